@@ -11,12 +11,17 @@ timed step (the assembled image is on every rank at the end of each step);
 the rejection totals are all-reduced once at the end.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config winsorized100]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints one JSON line.  `roofline` uses the dominant kernel's time
-measured with HIP events on its own stream (sgpu_last_timing); `cpu_baseline`
-times the oracle (C restatement, OpenMP) on a bounded sample of the same
-workload, on rank 0 at N=1 only.
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K
+steps and prints the line; `roofline` uses the dominant kernel's time
+measured with HIP events on its own stream (sgpu_last_timing) inside those
+steps.  `--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy (dump_outputs below).  `--full` adds what takes runs of its
+own after the timed steps, on rank 0 at N=1 only: `cpu_baseline` times the
+oracle (C restatement, OpenMP) on a bounded sample of the same workload, and
+`parity` compares one extra GPU stack of those rows with it bit for bit.
 """
 from __future__ import annotations
 
@@ -103,7 +108,14 @@ def parse():
     ap.add_argument("--config", default="winsorized100", choices=sorted(CONFIGS) + sorted(AUX_CONFIGS))
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="target duration of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline and, for the stack configs, the "
+                         "bit-for-bit parity check against it (off by default: a plain run only times its steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline and the parity check out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy "
+                         "(float32 / float64, large arrays as a fixed seeded sample of rows)")
     ap.add_argument("--band-rows", type=int, default=0,
                     help="stack configs, one GPU: time one rank's row band of this many rows (e.g. 500 = "
                          "an 8-GPU rank's band of a 4000-row frame) instead of the whole frame")
@@ -115,7 +127,42 @@ def parse():
     ap.add_argument("--pipeline", type=int, default=4,
                     help="frame-sharded input: row sub-chunks of the transpose pipelined under the stack "
                          "(stack_frame_sharded_pipelined); 0 or 1 = one all-to-all of the whole band, then the stack")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    a.cpu_checks = a.full and not a.no_cpu_baseline
+    return a
+
+
+DUMP_LIMIT_BYTES = 48 << 20      # all files of one --dump-outputs run together (the contract allows 64 MB)
+DUMP_SEED = 20260821
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: the arrays the last timed step handed to its caller,
+    one DIR/<name>.npy each: float32 stays float32, everything else (64-bit
+    floats, integer counts and shifts) is written as float64.  An array above
+    its share of DUMP_LIMIT_BYTES is written as a fixed sample of its rows
+    (the last axis kept whole; the row indices, drawn once from DUMP_SEED, go
+    to <name>_rows.npy) together with <name>_colsum.npy, the float64 sum over
+    ALL rows of every column, so every element still bears on the dump."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, arr in arrays.items():
+        if hasattr(arr, "detach"):
+            arr = arr.detach().cpu().numpy()
+        arr = np.asarray(arr)
+        arr = np.ascontiguousarray(arr if arr.dtype == np.float32 else arr.astype(np.float64))
+        if arr.nbytes > share:
+            rows = arr.reshape(-1, arr.shape[-1]) if arr.ndim > 1 else arr.reshape(-1, 1)
+            # share = the kept rows + one float64 index each + the column sums
+            keep = max(1, min(rows.shape[0], (share - rows.shape[1] * 8) // (rows.shape[1] * rows.itemsize + 8)))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=keep, replace=False))
+            np.save(os.path.join(dirpath, name + "_rows.npy"), idx.astype(np.float64))
+            np.save(os.path.join(dirpath, name + "_colsum.npy"), rows.sum(axis=0, dtype=np.float64))
+            arr = rows[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
 
 
 def host_cpu():
@@ -415,14 +462,17 @@ def main():
     pipelined = sharded and a.pipeline > 1
     pev = []                                       # pipelined: per step, the sub-chunks' stack events
     prej = [0, 0]
+    last = {}                                      # pipelined: what the latest step returned
 
     def step():
         if pipelined:
             # transpose in a.pipeline row sub-chunks under the stack, then
             # the all-gather of the output bands (inside the function)
             st = {}
-            _, rej = stack_frame_sharded_pipelined(frames, n, args, method, ctx=ctx, subchunks=a.pipeline, stats=st,
-                                                   ctxs=ctxs)
+            img, rej = stack_frame_sharded_pipelined(frames, n, args, method, ctx=ctx, subchunks=a.pipeline, stats=st,
+                                                     ctxs=ctxs)
+            if a.dump_outputs:
+                last["result"], last["rejected"] = img, [int(rej[0]), int(rej[1])]
             pev.append(st["events"])
             prej[0] += rej[0]
             prej[1] += rej[1]
@@ -455,7 +505,9 @@ def main():
     torch.cuda.synchronize()
     with ClockSampler(dev) as clk:
         t0 = time.perf_counter()
-        for _ in range(a.steps):
+        for i in range(a.steps):
+            if a.dump_outputs and not pipelined and i == a.steps - 1:
+                before_last = counts.clone()        # the last step's own rejection totals (device copy, no sync)
             step()
             if not pipelined:
                 kern_ms.append(ctx.last_timing())   # syncs the stream after each step
@@ -464,6 +516,20 @@ def main():
             dist.barrier()
         elapsed = time.perf_counter() - t0
     ctx.set_timing(False)
+    if a.dump_outputs:
+        # the assembled image and the rejection totals (low, high) of the last
+        # timed step, summed over the ranks' bands like the totals of the line
+        if pipelined:
+            dump = dict(last)
+        else:
+            last_counts = counts - before_last
+            if world > 1:
+                dist.all_reduce(last_counts)
+            dump = {"result": full if full is not None else out, "rejected": last_counts}
+        if rank == 0:
+            dump_outputs(a.dump_outputs, dump)
+        del dump
+        last.clear()
     a2a_ms = sum(e0.elapsed_time(e1) for e0, e1 in xev) / len(xev) if xev else None
     if pipelined:
         # kernel time of a step = the sum of its sub-chunk stacks (HIP events
@@ -570,7 +636,7 @@ def main():
         # rejection totals per step (one stack); summed over the bands of all ranks
         "rejected_per_step": [int(x) // a.steps for x in counts.tolist()],
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.cpu_checks:
         res["cpu_baseline"], ref = cpu_baseline(frames, int(rt), sig, method, a.cpu_seconds, u16, norm)
         res["cpu_baseline"]["gpu_over_cpu"] = round(value / res["cpu_baseline"]["value"], 1)
         res["parity"] = parity_vs_oracle(ctx, S, frames, args, method, ref, u16)
@@ -765,6 +831,7 @@ def bench_aux(a):
     ctx.set_stream(stream.cuda_stream)
     res = {"n_gpus": world, "steps": a.steps, "warmup": a.warmup, "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "f32"}
+    dump = {}                                      # --dump-outputs: what the last timed step returned
     if kind == "RL":
         from siril_amd import deconvolution as D
         from siril_amd._lib import lib
@@ -778,6 +845,7 @@ def bench_aux(a):
             assert rc == 0
 
         elapsed, kern = _timed(step, a.steps, a.warmup, world, ctx, dev)
+        dump["deconvolved"] = work
         flops = lib().sgpu_rl_last_iter_flops(ctx.h)
         fft_convs = int(lib().sgpu_rl_last_fft_convs(ctx.h))
         it_bytes = lib().sgpu_rl_last_iter_bytes(ctx.h)
@@ -814,7 +882,7 @@ def bench_aux(a):
                        "fft_convs_per_step": fft_convs},
             "roofline": roof,
         })
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and a.cpu_checks:
             res["cpu_baseline"] = cpu_baseline_rl(obs, K, iters, a.cpu_seconds)
     elif kind == "RCD":
         import numpy as np
@@ -833,6 +901,7 @@ def bench_aux(a):
             Dm.debayer(mos, pattern=0, out=rgb, ctx=ctx, interpolation=interp)
 
         elapsed, kern = _timed(step, a.steps, a.warmup, world, ctx, dev)
+        dump["rgb"] = rgb
         pipe_ms = sum(k[0] for k in kern) / len(kern)
         alg_bytes = 16 * w * h            # read the CFA frame once, write 3 planes
         achieved = alg_bytes / (pipe_ms / 1e3) / 1e9
@@ -856,7 +925,7 @@ def bench_aux(a):
                          "pipeline_ms": round(pipe_ms, 3),
                          "alg_bytes_per_step": alg_bytes},
         })
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and a.cpu_checks:
             from oracle import demosaic_ref as Do
             crop = mos[:1000, :1500].cpu().numpy()
             t0 = time.perf_counter()
@@ -878,6 +947,7 @@ def bench_aux(a):
         def step():
             st = Nz.norm_stats_device(ctx, frames, lite=False)
             assert not st.status.any()
+            dump.update(median=st.median, mad=st.mad, location=st.location, scale=st.scale, ngood=st.ngood)
 
         elapsed, _ = _timed(step, a.steps, a.warmup, world, ctx, dev)
         # 9 streaming passes over every frame: 4 count/min/max, 4 histogram, 1 bwmv
@@ -897,7 +967,7 @@ def bench_aux(a):
                          "kernel": "norm_stats pipeline (k_minmax x4, k_hist x4, k_bwmv, k_select x4)",
                          "alg_bytes_per_step": alg_bytes, "passes": passes},
         })
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and a.cpu_checks:
             from oracle import oracle as O
             O.build()
             one = frames[0].cpu().numpy()
@@ -962,6 +1032,8 @@ def bench_aux(a):
                 stats.append(ctx.last_seq_stats())
 
             elapsed, _ = _timed(step, a.steps, a.warmup, world, ctx, dev)
+            if a.dump_outputs:
+                dump["result"] = Q.read_fits(outp)     # the image the command wrote
             st = stats[-a.steps:]
             mean = lambda k: sum(x[k] for x in st) / len(st)
             h2d_gbs = mean("h2d_bytes") / (mean("h2d_ms") / 1e3) / 1e9 if mean("h2d_ms") else None
@@ -1011,6 +1083,8 @@ def bench_aux(a):
             Q.run_command(f"stack {seq} rej n -nonorm -32b -out={outp}", ctx)
 
         elapsed, kern = _timed(step, a.steps, a.warmup, world, ctx, dev)
+        if a.dump_outputs:
+            dump["result"] = Q.read_fits(outp)         # the image the command wrote
         kern_ms = sum(k[0] for k in kern) / len(kern)
         alg_bytes = n * w * h * 4 + w * h * 4
         res.update({
@@ -1026,7 +1100,7 @@ def bench_aux(a):
                          "kernel": "k_stack_mean (per block, last block timed)", "kernel_ms": round(kern_ms, 4),
                          "note": "end-to-end step is host I/O bound (FITS read/convert, PCIe)"},
         })
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and a.cpu_checks:
             from oracle import oracle as O
             O.build()
             threads = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or min(16, os.cpu_count() or 1)
@@ -1061,6 +1135,7 @@ def bench_aux(a):
         # the pipeline time comes from HIP events the library records on the
         # stream it launches on (sgpu_last_timing ms[0])
         elapsed, kern = _timed(step, a.steps, a.warmup, world, ctx, dev)
+        dump.update(shifts=box["s"][0], quality=box["s"][1], best=[box["s"][2]])
         gpu_ms = sum(k[0] for k in kern) / len(kern)
         # DESIGN.md 4.4 traffic model, B per selection pixel (a half-spectrum
         # plane is 4 B/px): per frame rows fwd 4 + 4, fused columns (plane,
@@ -1091,7 +1166,7 @@ def bench_aux(a):
                                     "DFT half-spectrum pipeline (row pairs fwd into the column layout, columns fwd + xpow + columns bwd, C2R row pairs + argmax)"),
                          "pipeline_ms": round(gpu_ms, 3), "alg_bytes_per_step": alg_bytes},
         })
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and a.cpu_checks:
             res["cpu_baseline"] = cpu_baseline_dft(frames, Ssel, a.cpu_seconds)
     res["gpu_clock"] = _LAST_CLOCK
     traffic, src = aux_traffic(a.config)
@@ -1100,6 +1175,8 @@ def bench_aux(a):
         res["roofline"]["traffic_unit"] = "HBM bytes per step (FETCH_SIZE x 2 + WRITE_SIZE, rocprofv3 --pmc)"
         res["roofline"]["traffic_profile"] = src
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, dump)
         if res.get("cpu_baseline"):
             res["cpu_baseline"]["gpu_over_cpu"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
         else:

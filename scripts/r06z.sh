@@ -25,7 +25,7 @@ run() {
 if [ "$PART" = all ] || [ "$PART" = 1 ]; then
 run pytest_gpu 800 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -rf
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-run bench 600 python bench.py --steps 20 --warmup 5
+run bench 600 python bench.py --steps 20 --warmup 5 --full
 run prof 600 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline
 run prof_mean100 600 rocprofv3 --kernel-trace --stats -d "$O/prof_mean100" -o run --output-format csv -- python bench.py --config mean100 --steps 20 --warmup 5 --no-cpu-baseline
 run pmc_w 900 bash scripts/pmc_session.sh "$T/pmc_w" winsorized100 k_stack
@@ -39,7 +39,7 @@ done
 fi
 if [ "$PART" = all ] || [ "$PART" = 2 ] || [ "$PART" = 2b ]; then
 for c in sigma400 mean100 median100 winsorized100_u16 winsorized128 winsorized12_s1 dft100 rl63 rl63_direct rcd bayerfast norm100 fits10 seq100; do
-  run b_$c 600 python bench.py --config $c --steps 10 --warmup 3
+  run b_$c 600 python bench.py --config $c --steps 10 --warmup 3 --full
 done
 fi
 if [ "$PART" = all ] || [ "$PART" = 3 ]; then

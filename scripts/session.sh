@@ -29,11 +29,11 @@ for s in $STEPS; do
     fscheck) run fscheck 400 python scripts/fs_check.py 100 4000 6000;;
     fs_*) x=${s#fs_}; cfg=${x%_p*}; k=${x##*_p}; run "fs_${cfg}_p$k" 600 python bench.py --config "$cfg" --input frame-sharded --pipeline "$k" --steps 3 --warmup 1 --no-cpu-baseline;;
     band_*) x=${s#band_}; cfg=${x%_*}; r=${x##*_}; run "band_${cfg}_$r" 600 python bench.py --config "$cfg" --band-rows "$r" --steps 10 --warmup 3 --no-cpu-baseline;;
-    bench) run bench 600 python bench.py --steps 20 --warmup 5;;
+    bench) run bench 600 python bench.py --steps 20 --warmup 5 --full;;
     prof) run prof 600 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline;;
     pmc) run pmc 900 bash scripts/pmc_session.sh "$TAG/pmc_w" winsorized100 k_stack_sorted;;
     pmc_s400) run pmc_s400 900 bash scripts/pmc_session.sh "$TAG/pmc_s400" sigma400 k_stack_sorted;;
-    bench_*) cfg=${s#bench_}; run "b_$cfg" 600 python bench.py --config "$cfg" --steps 5 --warmup 2;;
+    bench_*) cfg=${s#bench_}; run "b_$cfg" 600 python bench.py --config "$cfg" --steps 5 --warmup 2 --full;;
     traffic_*) cfg=${s#traffic_}; run "tr_$cfg" 600 bash scripts/pmc_traffic.sh "$TAG/tr_$cfg" "$cfg";;
     sprof_*) cfg=${s#sprof_}; run "sp_$cfg" 300 env SGPU_LIB=variants/prof/libsirilgpu.so SGPU_PROF=1 python bench.py --config "$cfg" --steps 1 --warmup 1 --no-cpu-baseline;;
     prof_*) cfg=${s#prof_}; run "p_$cfg" 600 rocprofv3 --kernel-trace --stats -d "$O/p_$cfg" -o run --output-format csv -- python bench.py --config "$cfg" --steps 5 --warmup 2 --no-cpu-baseline;;

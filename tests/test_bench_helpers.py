@@ -22,6 +22,43 @@ def test_clock_sampler_reads_current_level(tmp_path):
     assert cs.summary()["sclk_mhz_median"] is None
 
 
+def test_plain_run_is_lean_and_full_adds_the_cpu_checks(monkeypatch):
+    """The CPU baseline and the parity check run only behind --full."""
+    import bench
+    for argv, want in (([], False), (["--full"], True), (["--full", "--no-cpu-baseline"], False),
+                       (["--no-cpu-baseline"], False)):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"] + argv)
+        a = bench.parse()
+        assert (a.steps, a.warmup, a.cpu_checks, a.dump_outputs) == (3, 1, want, None)
+
+
+def test_dump_outputs_formats_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 files; an array above its share is a
+    seeded row sample (the same rows every run) plus its full column sums."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 4096)
+    rng = np.random.default_rng(1)
+    img = rng.random((50, 64), dtype=np.float32)             # 12 800 B > the 4 096 B share
+    counts = np.array([7, 2 ** 40 + 1], np.int64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"result": img, "rejected": counts})
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    b = {f: np.load(tmp_path / "b" / f) for f in sorted(os.listdir(tmp_path / "b"))}
+    assert sorted(a) == ["rejected.npy", "result.npy", "result_colsum.npy", "result_rows.npy"]
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    assert a["rejected.npy"].dtype == np.float64 and a["rejected.npy"].tolist() == [7.0, float(2 ** 40 + 1)]
+    rows = a["result_rows.npy"].astype(int)
+    assert a["result.npy"].dtype == np.float32 and 1 <= len(rows) < 50 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["result.npy"], img[rows])
+    assert np.array_equal(a["result_colsum.npy"], img.sum(axis=0, dtype=np.float64))
+    assert sum(v.nbytes for v in a.values()) <= 2 * 4096
+    # below its share an array is written whole
+    bench.dump_outputs(str(tmp_path / "c"), {"result": img[:8]})
+    assert os.listdir(tmp_path / "c") == ["result.npy"]
+    assert np.array_equal(np.load(tmp_path / "c" / "result.npy"), img[:8])
+
+
 def test_traffic_records_match_sources():
     """Every committed per-step traffic record names its profile file, and a
     record is only used while the kernel sources hash the same."""
