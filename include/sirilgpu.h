@@ -468,9 +468,43 @@ int sgpu_shift_frames_device(sgpu_context *ctx, const void *d_in, void *d_out, i
  * shift; 0-4: cvTransformImage, which for an integer translation samples
  * every kernel at phase 0, i.e. the same exact shift.  Homographies other
  * than translations, and sub-pixel translations with 0-4, return
- * SGPU_BAD_ARGUMENT.  Frames as sgpu_shift_frames_device.  Synchronous. */
+ * SGPU_BAD_ARGUMENT here: those resample, which is sgpu_warp_frames_device
+ * below.  Frames as sgpu_shift_frames_device.  Synchronous. */
 int sgpu_apply_reg_device(sgpu_context *ctx, const void *d_in, void *d_out, int elem_size, int nframes,
 		int width, int height, long frame_stride, const double *H, int ref_index, int interpolation);
+
+/* ---- resampling warp (apply_reg with an OpenCV interpolation) ------------ */
+
+/* cvTransformImage (opencv/opencv.cpp) at scale 1, FRAMING_CURRENT, on
+ * nframes device frames (layout as sgpu_shift_frames_device; elem_size 4:
+ * float, 2: WORD): frame f is resampled through Href^-1 * Hf (H: 9 doubles
+ * per frame, h00..h22, top-down pixel coordinates as Siril stores them) with
+ * interpolation OPENCV_NEAREST 0, LINEAR 1, CUBIC 2, AREA 3 (= LINEAR, as
+ * warpPerspective treats it) or LANCZOS4 4, zero where the source pixel is
+ * outside the frame (BORDER_TRANSPARENT over a zeroed destination),
+ * reflect-101 taps.  clamp != 0 with CUBIC / LANCZOS4: pixels that undershoot
+ * 0.98 x the LINEAR warp, and their 4-neighbours, take the LINEAR value.
+ * The arithmetic (fixed-point 1/32 pixel phases, float coefficient tables,
+ * summation order) is the specification in DESIGN.md "Frame warp", modelled
+ * on OpenCV's warpPerspective -> remap path; parity against a real OpenCV
+ * build is unpinned.  d_out must not alias d_in.  Bad sizes, interpolation
+ * outside 0..4 and singular or non-finite maps return SGPU_BAD_ARGUMENT.
+ * Synchronous. */
+int sgpu_warp_frames_device(sgpu_context *ctx, const void *d_in, void *d_out, int elem_size, int nframes,
+		int width, int height, long frame_stride, const double *H, int ref_index, int interpolation,
+		int clamp);
+/* The destination -> source maps sgpu_warp_frames_device uses, 9 doubles per
+ * frame in M: the inverse of F * (Href^-1 * Hf) * F, F the row flip of a
+ * `height`-row frame (frames are held bottom-up).  Host only. */
+int sgpu_warp_inverse_maps(int nframes, const double *H, int ref_index, int height, double *M);
+/* The 32-phase coefficient table of an interpolation: tab[32 * taps], taps
+ * returned in *taps (NEAREST 1, LINEAR and AREA 2, CUBIC 4, LANCZOS4 8).
+ * Host only. */
+int sgpu_warp_table(int interpolation, float *tab, int *taps);
+/* Output tiles of the last sgpu_warp_frames_device call that resampled from
+ * an LDS-staged source patch (counts[0]) and that gathered from global
+ * memory (counts[1]). */
+int sgpu_warp_last_tiles(sgpu_context *ctx, long counts[2]);
 
 /* ---- CFA helpers -------------------------------------- */
 

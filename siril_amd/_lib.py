@@ -44,6 +44,7 @@ EXPORTS = (
     "sgpu_set_input_bitpix", "sgpu_stack_seq_opts", "sgpu_stack_seq_frames",
     "sgpu_stack_blocks", "sgpu_feather_mask_size", "sgpu_feather_masks_device", "sgpu_feather_block_area",
     "sgpu_feather_block_device", "sgpu_set_seq_readers", "sgpu_last_seq_stats", "sgpu_release_seq_buffers",
+    "sgpu_warp_frames_device", "sgpu_warp_inverse_maps", "sgpu_warp_table", "sgpu_warp_last_tiles",
 )
 
 SGPU_OK = 0
@@ -309,6 +310,14 @@ def lib():
         L.sgpu_apply_reg_shifts.argtypes = [i, vp, vp, i, vp, vp]
         L.sgpu_shift_frames_device.restype = i
         L.sgpu_shift_frames_device.argtypes = [vp, vp, vp, i, i, i, i, C.c_long, vp, vp]
+        L.sgpu_warp_frames_device.restype = i
+        L.sgpu_warp_frames_device.argtypes = [vp, vp, vp, i, i, i, i, C.c_long, vp, i, i, i]
+        L.sgpu_warp_inverse_maps.restype = i
+        L.sgpu_warp_inverse_maps.argtypes = [i, vp, i, i, vp]
+        L.sgpu_warp_table.restype = i
+        L.sgpu_warp_table.argtypes = [i, vp, pi]
+        L.sgpu_warp_last_tiles.restype = i
+        L.sgpu_warp_last_tiles.argtypes = [vp, C.POINTER(C.c_long)]
         L.sgpu_extract_cfa_device.restype = i
         L.sgpu_extract_cfa_device.argtypes = [vp, vp, i, i, i, vp, i, i, vp, C.POINTER(C.c_long)]
         L.sgpu_cfa_count.restype = C.c_long

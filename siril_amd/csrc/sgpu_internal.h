@@ -127,6 +127,11 @@ struct sgpu_context {
     sgpu_host::DevBuf onorm;
     // overlap normalization: packed pair samples and the pair table
     sgpu_host::DevBuf ov_ws, ov_tab;
+    // frame warp: tile counters, per-frame inverse maps and coefficient tables
+    // (one device block, one host image of it that outlives the async upload)
+    sgpu_host::DevBuf warp_ws;
+    std::vector<double> h_warp;
+    unsigned long long warp_tiles[2] = {0, 0};   // last call: staged, direct
 
     void release_all() {
         for (sgpu_host::DevBuf *b : {&fb_list, &fb_count, &counts, &scratch, &scale, &offset, &mul,
@@ -134,7 +139,7 @@ struct sgpu_context {
                                      &dft_tw, &dft_ref, &dft_t1, &dft_t2, &dft_best, &dft_shifts,
                                      &dft_frames, &rl_u, &rl_e, &rl_f, &rl_r, &rl_w, &rl_taps, &rl_small,
                                      &rl_io, &rl_reg, &rl_gxy, &rlf_t1, &rlf_t2, &rlf_ka, &rlf_kb, &rlf_kt, &rlf_tw1, &rlf_tw2, &dm_ws, &dm_mm, &dm_io, &ns_state, &ns_hist, &ns_part, &ns_io, &bn_rows, &qe_buf, &qe_part, &qe_io, &onorm, &ov_ws, &ov_tab,
-                                     &fb2_list, &fb2_count, &wz_ws, &wz_cnt, &fe_tab, &fe_dt, &cfa_tmp, &cstripe,
+                                     &fb2_list, &fb2_count, &wz_ws, &wz_cnt, &fe_tab, &fe_dt, &cfa_tmp, &cstripe, &warp_ws,
                                      &seq_in[0], &seq_in[1], &seq_out, &seq_lo, &seq_hi, &seq_cnt})
             b->release();
         seq_pin[0].release();

@@ -271,3 +271,59 @@ def apply_reg(frames, Hs, ref_index: int, interpolation: int = OPENCV_LANCZOS4, 
                                       frames.element_size(), n, w, h, h * w, H.ctypes.data_as(C.c_void_p), ref_index,
                                       int(interpolation)), "sgpu_apply_reg_device")
     return out
+
+
+# ---- applying the registration with resampling (cvTransformImage) ----------
+def warp_inverse_maps(Hs, ref_index: int, height: int) -> np.ndarray:
+    """The destination -> source maps warp_frames uses ([N, 9] float64): the
+    inverse of F * (Href^-1 * Hf) * F, F the row flip of a `height`-row frame
+    (sgpu_warp_inverse_maps).  Singular or non-finite maps raise SgpuError."""
+    H = np.ascontiguousarray(np.asarray(Hs, np.float64).reshape(-1, 9))
+    M = np.zeros_like(H)
+    check(lib().sgpu_warp_inverse_maps(H.shape[0], H.ctypes.data_as(C.c_void_p), int(ref_index), int(height),
+                                       M.ctypes.data_as(C.c_void_p)), "sgpu_warp_inverse_maps")
+    return M
+
+
+def warp_table(interpolation: int) -> np.ndarray:
+    """The [32, taps] float32 coefficient table of an interpolation
+    (OPENCV_NEAREST..OPENCV_LANCZOS4), one row per 1/32-pixel phase."""
+    tab = np.zeros(32 * 8, np.float32)
+    taps = C.c_int(0)
+    check(lib().sgpu_warp_table(int(interpolation), tab.ctypes.data_as(C.c_void_p), C.byref(taps)), "sgpu_warp_table")
+    return tab[:32 * taps.value].reshape(32, taps.value).copy()
+
+
+def warp_last_tiles(ctx) -> tuple:
+    """(staged, direct): output tiles of ctx's last warp_frames call that read
+    an LDS-staged source patch, and that gathered from global memory."""
+    cnt = (C.c_long * 2)()
+    check(lib().sgpu_warp_last_tiles(ctx.h, cnt), "sgpu_warp_last_tiles")
+    return int(cnt[0]), int(cnt[1])
+
+
+def warp_frames(frames, Hs, ref_index: int, interpolation: int = OPENCV_LANCZOS4, clamp: bool = True, out=None,
+                ctx=None):
+    """apply_reg with resampling (cvTransformImage at scale 1,
+    FRAMING_CURRENT): frames [N, H, W] CUDA tensor (float32 or 16-bit WORD
+    storage), Hs [N, 3, 3] homographies; frame f is warped through
+    Href^-1 * Hf with OPENCV_NEAREST / LINEAR / CUBIC / AREA / LANCZOS4, zero
+    outside the source frame; `clamp` applies Siril's undershoot clamp to
+    CUBIC and LANCZOS4.  `out` must not alias `frames`.  The arithmetic is
+    the specification in DESIGN.md "Frame warp" (OpenCV parity unpinned)."""
+    import torch
+    from .stacking import Context
+    ctx = ctx or Context(frames.device.index or 0)
+    if frames.dim() != 3 or not frames.is_cuda or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous CUDA tensor [N, H, W]")
+    n, h, w = frames.shape
+    H = np.ascontiguousarray(np.asarray(Hs, np.float64).reshape(n, 9))
+    out = torch.empty_like(frames) if out is None else out
+    if out.shape != frames.shape or out.dtype != frames.dtype or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous CUDA tensor like frames")
+    ctx.set_stream(torch.cuda.current_stream(frames.device).cuda_stream)
+    check(lib().sgpu_warp_frames_device(ctx.h, C.c_void_p(frames.data_ptr()), C.c_void_p(out.data_ptr()),
+                                        frames.element_size(), n, w, h, h * w, H.ctypes.data_as(C.c_void_p),
+                                        int(ref_index), int(interpolation), int(bool(clamp))),
+          "sgpu_warp_frames_device")
+    return out
