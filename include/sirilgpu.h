@@ -506,6 +506,60 @@ int sgpu_warp_table(int interpolation, float *tab, int *taps);
  * memory (counts[1]). */
 int sgpu_warp_last_tiles(sgpu_context *ctx, long counts[2]);
 
+/* ---- calibration (the `calibrate` command: preprocess()) ------------------ */
+
+/* Arithmetic: the specification in DESIGN.md "Calibration" (S1-S7), restated
+ * in tests/calib_ref.py; parity with a Siril binary is unpinned.  Masters are
+ * float planes (width x height, [0,1] units) in device memory.  All of these
+ * run on the context's stream and are synchronous unless noted. */
+
+#define SGPU_COLD_PIXEL 0
+#define SGPU_HOT_PIXEL  1
+
+/* S4: count / mean / sigma of the samples v != 0, not NaN, of the region
+ * [x0, x1) x [y0, y1) of a device plane, visiting every `step`-th column and
+ * row from (x0, y0) (step 1, or 2 for one Bayer site): double row sums left
+ * to right, rows combined top to bottom. */
+int sgpu_region_stats_device(sgpu_context *ctx, const float *d_plane, int width, int height, int x0, int y0,
+		int x1, int y1, int step, long *n, double *mean, double *sigma);
+/* S5: -equalize_cfa of a Bayer flat (pattern_size 2; 6, X-Trans, returns
+ * SGPU_BAD_ARGUMENT): d_out = d_flat with the two non-green sites multiplied
+ * by coef[0], coef[1] (returned); *green_diag 0 when sites 0 and 3 are green,
+ * 1 when sites 1 and 2 are.  d_out may be d_flat. */
+int sgpu_equalize_cfa_flat_device(sgpu_context *ctx, const float *d_flat, float *d_out, int width, int height,
+		int pattern_size, float coef[2], int *green_diag);
+/* S6: the deviant pixels of a master dark at median -/+ cold/hot sigma (-1:
+ * none of that kind), in raster order, as (y*width + x, SGPU_COLD_PIXEL or
+ * SGPU_HOT_PIXEL) int pairs in d_list.  *count is always the number found;
+ * the list is written only when d_list is given and count <= capacity.
+ * stats (optional): median, sigma, thresHot, thresCold. */
+int sgpu_find_deviant_pixels_device(sgpu_context *ctx, const float *d_dark, int width, int height, double cold,
+		double hot, int *d_list, long capacity, long *count, double stats[4]);
+/* S7: cosmeticCorrection of nframes float device frames in place, bit for
+ * bit the sequential loop over the list for any list.  The launch plan
+ * (dependency levels) is kept in the context and rebuilt when the list,
+ * the frame size or cfa changes. */
+int sgpu_cosmetic_correction_device(sgpu_context *ctx, float *d_frames, int nframes, int width, int height,
+		long frame_stride, const int *d_list, long count, int cfa);
+/* S3: the dark-optimisation factor of every frame (elem_size 2: WORD, 4:
+ * float; frame f at d_in + f*frame_stride samples) in one launch: d_k[nframes]
+ * on the device (optional) and k_host[nframes] (optional; without it the call
+ * is asynchronous).  Bias: d_bias plane, else bias_level when use_level. */
+int sgpu_dark_optimize_device(sgpu_context *ctx, const void *d_in, int elem_size, int nframes, int width,
+		int height, long frame_stride, const float *d_bias, int use_level, float bias_level,
+		const float *d_dark, float *d_k, float *k_host);
+/* S1 + S2 (+ S3 with dark_optim, + S7 with a deviant list): calibrate nframes
+ * device frames into float frames d_out (same frame_stride, in floats).
+ * d_bias / d_dark / d_flat optional; norm multiplies the flat quotient.  d_k:
+ * optional device factors k[nframes] of the dark -- read, or written first
+ * when dark_optim.  d_out may be d_in only for float input.  elem_size other
+ * than 2 or 4, frame_stride < width*height, an aliased WORD input, and
+ * dark_optim or a deviant list without a dark return SGPU_BAD_ARGUMENT. */
+int sgpu_calibrate_frames_device(sgpu_context *ctx, const void *d_in, float *d_out, int elem_size, int nframes,
+		int width, int height, long frame_stride, const float *d_bias, int use_level, float bias_level,
+		const float *d_dark, const float *d_flat, float norm, float *d_k, const int *d_list, long count,
+		int cfa, int dark_optim);
+
 /* ---- CFA helpers -------------------------------------- */
 
 /* extract_CFA_buffer_float (algos/demosaicing.c:936-975) on a device image:

@@ -45,6 +45,8 @@ EXPORTS = (
     "sgpu_stack_blocks", "sgpu_feather_mask_size", "sgpu_feather_masks_device", "sgpu_feather_block_area",
     "sgpu_feather_block_device", "sgpu_set_seq_readers", "sgpu_last_seq_stats", "sgpu_release_seq_buffers",
     "sgpu_warp_frames_device", "sgpu_warp_inverse_maps", "sgpu_warp_table", "sgpu_warp_last_tiles",
+    "sgpu_region_stats_device", "sgpu_equalize_cfa_flat_device", "sgpu_find_deviant_pixels_device",
+    "sgpu_cosmetic_correction_device", "sgpu_dark_optimize_device", "sgpu_calibrate_frames_device",
 )
 
 SGPU_OK = 0
@@ -318,6 +320,20 @@ def lib():
         L.sgpu_warp_table.argtypes = [i, vp, pi]
         L.sgpu_warp_last_tiles.restype = i
         L.sgpu_warp_last_tiles.argtypes = [vp, C.POINTER(C.c_long)]
+        pl, pd = C.POINTER(C.c_long), C.POINTER(C.c_double)
+        L.sgpu_region_stats_device.restype = i
+        L.sgpu_region_stats_device.argtypes = [vp, vp, i, i, i, i, i, i, i, pl, pd, pd]
+        L.sgpu_equalize_cfa_flat_device.restype = i
+        L.sgpu_equalize_cfa_flat_device.argtypes = [vp, vp, vp, i, i, i, C.POINTER(f), pi]
+        L.sgpu_find_deviant_pixels_device.restype = i
+        L.sgpu_find_deviant_pixels_device.argtypes = [vp, vp, i, i, C.c_double, C.c_double, vp, C.c_long, pl, pd]
+        L.sgpu_cosmetic_correction_device.restype = i
+        L.sgpu_cosmetic_correction_device.argtypes = [vp, vp, i, i, i, C.c_long, vp, C.c_long, i]
+        L.sgpu_dark_optimize_device.restype = i
+        L.sgpu_dark_optimize_device.argtypes = [vp, vp, i, i, i, i, C.c_long, vp, i, f, vp, vp, vp]
+        L.sgpu_calibrate_frames_device.restype = i
+        L.sgpu_calibrate_frames_device.argtypes = [vp, vp, vp, i, i, i, i, C.c_long, vp, i, f, vp, vp, f, vp, vp,
+                                                   C.c_long, i, i]
         L.sgpu_extract_cfa_device.restype = i
         L.sgpu_extract_cfa_device.argtypes = [vp, vp, i, i, i, vp, i, i, vp, C.POINTER(C.c_long)]
         L.sgpu_cfa_count.restype = C.c_long
