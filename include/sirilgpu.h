@@ -50,7 +50,7 @@ enum sgpu_method { SGPU_METHOD_MEAN = 0, SGPU_METHOD_MEDIAN = 1 };
  * their _device variants take `lambda` before maxiter, as the reference's
  * fft_richardson_lucy does).  A caller compiled against this header checks
  * sgpu_abi_version() == SGPU_ABI_VERSION before its first call. */
-#define SGPU_ABI_VERSION 4
+#define SGPU_ABI_VERSION 5
 int sgpu_abi_version(void);
 
 typedef struct sgpu_context sgpu_context;
@@ -559,6 +559,87 @@ int sgpu_calibrate_frames_device(sgpu_context *ctx, const void *d_in, float *d_o
 		int width, int height, long frame_stride, const float *d_bias, int use_level, float bias_level,
 		const float *d_dark, const float *d_flat, float norm, float *d_k, const int *d_list, long count,
 		int cfa, int dark_optim);
+
+/* ---- star detection and star-based global registration ------------------- */
+
+/* Arithmetic: the specification in DESIGN.md 6f, restated in
+ * tests/star_ref.py; modelled on Siril's star_finder.c and matching/, with
+ * image moments in place of the PSF fit.  Parity with Siril is unpinned. */
+
+#define SGPU_NOT_REGISTERED 1   /* sgpu_match_stars: too few pairs; H is all zeros (the null homography) */
+
+typedef struct sgpu_star_params {
+	double ksigma;          /* threshold bg + ksigma * noise (1.0) */
+	double smooth_sigma;    /* Gaussian smoothing, 0 <= sigma <= 2, half-width ceil(3 sigma) (1.0) */
+	double roundness_min;   /* (0.5) */
+	double min_amp;         /* peak amplitude over bg, in units of noise (5.0) */
+	double cut;             /* moments use pixels above cut * amplitude (0.1) */
+	double min_fwhm;        /* pixels (1.0) */
+	double sat;             /* a peak sample >= sat is rejected (+inf) */
+	int radius;             /* local-maximum window and box half-size, 1..16 (10) */
+	int max_stars;          /* (2000) */
+	int keep_candidates;    /* keep every measured candidate for sgpu_star_last_candidates */
+	int reserved;
+} sgpu_star_params;
+
+typedef struct sgpu_star {
+	double x, y;            /* centroid, memory order, pixel centres at integers */
+	double flux;            /* S0 */
+	double amp;             /* peak sample - bg */
+	double fwhm_major, fwhm_minor, roundness;
+	int px, py;             /* the candidate pixel */
+	int npix;               /* pixels above the cut */
+	int ext[4];             /* box extents -x, +x, -y, +y */
+	int reject;             /* 0: accepted; 1 amplitude, 2 saturated, 3 flux or variance not positive,
+	                           4 fwhm_minor, 5 fwhm_major, 6 roundness (sgpu_star_last_candidates only) */
+} sgpu_star;
+
+typedef struct sgpu_match_params {
+	double tri_tol;         /* triangle ratio tolerance (0.002) */
+	double match_radius;    /* pixels (2.0) */
+	int nbright;            /* stars that form triangles (20) */
+	int min_pairs;          /* (10) */
+	int model;              /* SGPU_MODEL_* (homography) */
+	int reserved;
+} sgpu_match_params;
+#define SGPU_MODEL_SHIFT      0
+#define SGPU_MODEL_SIMILARITY 1
+#define SGPU_MODEL_AFFINE     2
+#define SGPU_MODEL_HOMOGRAPHY 3
+
+/* The defaults above. */
+void sgpu_star_default_params(sgpu_star_params *p);
+void sgpu_match_default_params(sgpu_match_params *p);
+/* The normalised Gaussian smoothing table: tab[2K + 1], K = ceil(3 sigma),
+ * *taps = 2K + 1 (sigma 0: {1}).  tab must hold 13 floats.  Host only. */
+int sgpu_star_smooth_table(double sigma, float *tab, int *taps);
+/* Stars of nframes device frames (elem_size 4: float, 2: WORD; sample (x, y)
+ * of frame f at d_frames + f*frame_stride + y*row_stride + x, in samples).
+ * bg[f], noise[f]: background level and noise of each frame, in sample
+ * units.  stars: nframes x max_stars records, the stars of frame f from
+ * stars[f * max_stars], brightest (flux) first, ties by (row, column);
+ * nstars[f] of them.  ncandidates (optional): local maxima found before
+ * measurement.  A frame with no interior pixel yields zero stars.  The
+ * result does not depend on launch or arrival order.  Parameters out of
+ * range return SGPU_BAD_ARGUMENT.  Synchronous. */
+int sgpu_find_stars_device(sgpu_context *ctx, const void *d_frames, int elem_size, int nframes, int width,
+		int height, long row_stride, long frame_stride, const double *bg, const double *noise,
+		const sgpu_star_params *params, sgpu_star *stars, int *nstars, long *ncandidates);
+/* Every candidate (accepted or not, `reject` says why) of one frame of the
+ * last sgpu_find_stars_device call made with keep_candidates, in raster
+ * order.  *count is always the number; cand is written when it fits. */
+int sgpu_star_last_candidates(sgpu_context *ctx, int frame, sgpu_star *cand, long capacity, long *count);
+/* Device time of the last sgpu_find_stars_device call: candidate pass
+ * (ms[0]) and measurement (ms[1]), milliseconds. */
+int sgpu_star_last_kernel_ms(sgpu_context *ctx, float ms[2]);
+/* Match two star lists (x, y pairs, brightest first, top-down pixel
+ * coordinates y_td = height-1 - y_mem) by triangle voting and fit the
+ * transform that maps frame (img) pixels to reference pixels, h22 = 1, as
+ * sgpu_warp_frames_device takes it.  pairs: (img, ref) index pairs, room for
+ * min(nref, nimg).  Returns SGPU_OK, or SGPU_NOT_REGISTERED with H all zeros
+ * and *npairs the pairs found.  Deterministic.  Host only. */
+int sgpu_match_stars(const double *ref_xy, int nref, const double *img_xy, int nimg, int width, int height,
+		const sgpu_match_params *params, double H[9], int *npairs, int *pairs);
 
 /* ---- CFA helpers -------------------------------------- */
 

@@ -47,11 +47,13 @@ EXPORTS = (
     "sgpu_warp_frames_device", "sgpu_warp_inverse_maps", "sgpu_warp_table", "sgpu_warp_last_tiles",
     "sgpu_region_stats_device", "sgpu_equalize_cfa_flat_device", "sgpu_find_deviant_pixels_device",
     "sgpu_cosmetic_correction_device", "sgpu_dark_optimize_device", "sgpu_calibrate_frames_device",
+    "sgpu_star_default_params", "sgpu_match_default_params", "sgpu_star_smooth_table", "sgpu_find_stars_device",
+    "sgpu_star_last_candidates", "sgpu_star_last_kernel_ms", "sgpu_match_stars",
 )
 
 SGPU_OK = 0
 SGPU_NO_DEVICE = -20
-ABI_VERSION = 4          # SGPU_ABI_VERSION of include/sirilgpu.h this binding is written against
+ABI_VERSION = 5          # SGPU_ABI_VERSION of include/sirilgpu.h this binding is written against
 
 
 class StackParams(C.Structure):
@@ -79,6 +81,19 @@ class StackSeqOptions(C.Structure):
         [(f, C.c_int) for f in ("f_fwhm_k", "f_wfwhm_k", "f_round_k", "f_quality_k", "f_bkg_k", "f_nbstars_k",
                                 "filter_included", "maximize", "overlap_norm", "feather")] + \
         [("max_block_bytes", C.c_long), ("block_threads", C.c_int), ("block_max_rows", C.c_long)]
+
+
+class StarParams(C.Structure):
+    """sgpu_star_params (include/sirilgpu.h)."""
+    _fields_ = [(f, C.c_double) for f in ("ksigma", "smooth_sigma", "roundness_min", "min_amp", "cut", "min_fwhm",
+                                          "sat")] + \
+        [(f, C.c_int) for f in ("radius", "max_stars", "keep_candidates", "reserved")]
+
+
+class MatchParams(C.Structure):
+    """sgpu_match_params (include/sirilgpu.h)."""
+    _fields_ = [("tri_tol", C.c_double), ("match_radius", C.c_double), ("nbright", C.c_int), ("min_pairs", C.c_int),
+                ("model", C.c_int), ("reserved", C.c_int)]
 
 
 class SgpuError(RuntimeError):
@@ -334,6 +349,21 @@ def lib():
         L.sgpu_calibrate_frames_device.restype = i
         L.sgpu_calibrate_frames_device.argtypes = [vp, vp, vp, i, i, i, i, C.c_long, vp, i, f, vp, vp, f, vp, vp,
                                                    C.c_long, i, i]
+        L.sgpu_star_default_params.restype = None
+        L.sgpu_star_default_params.argtypes = [C.POINTER(StarParams)]
+        L.sgpu_match_default_params.restype = None
+        L.sgpu_match_default_params.argtypes = [C.POINTER(MatchParams)]
+        L.sgpu_star_smooth_table.restype = i
+        L.sgpu_star_smooth_table.argtypes = [C.c_double, vp, pi]
+        L.sgpu_find_stars_device.restype = i
+        L.sgpu_find_stars_device.argtypes = [vp, vp, i, i, i, i, C.c_long, C.c_long, vp, vp, C.POINTER(StarParams),
+                                             vp, vp, vp]
+        L.sgpu_star_last_candidates.restype = i
+        L.sgpu_star_last_candidates.argtypes = [vp, i, vp, C.c_long, pl]
+        L.sgpu_star_last_kernel_ms.restype = i
+        L.sgpu_star_last_kernel_ms.argtypes = [vp, C.POINTER(f)]
+        L.sgpu_match_stars.restype = i
+        L.sgpu_match_stars.argtypes = [vp, i, vp, i, i, i, C.POINTER(MatchParams), vp, pi, vp]
         L.sgpu_extract_cfa_device.restype = i
         L.sgpu_extract_cfa_device.argtypes = [vp, vp, i, i, i, vp, i, i, vp, C.POINTER(C.c_long)]
         L.sgpu_cfa_count.restype = C.c_long

@@ -4,7 +4,12 @@ siril_amd/sequence.py).  Prints the output path and the rejection totals.
 
 `python -m siril_amd.cli calibrate <seq> [-bias=F | -bias="=LEVEL"] [-dark=F] [-flat=F] [-cc=dark [cold hot]]
 [-cfa] [-equalize_cfa] [-opt] [-prefix=pp_]`: the calibration step (siril_amd/calibration.py); writes 32-bit
-<prefix><name>NNNNN.fit and the new .seq."""
+<prefix><name>NNNNN.fit and the new .seq.
+
+`python -m siril_amd.cli register <seq> [-layer=N] [-transf=shift|similarity|affine|homography] [-minpairs=N]
+[-maxstars=N] [-noout] [-interp=ne|li|cu|ar|la] [-noclamp] [-prefix=r_]`: star-based global registration
+(siril_amd/registration.py); rewrites the .seq with the homographies and, unless -noout, writes the warped 32-bit
+<prefix><name>NNNNN.fit and their .seq."""
 import sys
 import time
 
@@ -17,6 +22,13 @@ def main(argv=None):
         out, k = run_calibrate(argv)
         print(f"Calibrated to {out} in {time.perf_counter() - t0:.3f} s" +
               ("" if k is None else "; dark factors " + " ".join(f"{v:.4f}" for v in k)))
+        return 0
+    if argv and argv[0] == "register":
+        from siril_amd.registration import run_register
+        t0 = time.perf_counter()
+        out, _, info = run_register(argv)
+        print(f"Registered to {out} in {time.perf_counter() - t0:.3f} s; {int(info['registered'].sum())} of "
+              f"{len(info['registered'])} frames, pairs " + " ".join(str(int(v)) for v in info["npairs"]))
         return 0
     if not argv or argv[0] != "stack":
         print(__doc__, file=sys.stderr)

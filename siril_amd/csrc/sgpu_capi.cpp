@@ -231,6 +231,8 @@ void sgpu_release(sgpu_context *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->release_all();
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->star_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->own) (void)hipStreamDestroy(c->own);
     delete c;
 }

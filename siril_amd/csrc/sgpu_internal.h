@@ -138,6 +138,11 @@ struct sgpu_context {
     std::vector<int> h_cal_list;          // deviant list the plan was built for (pos, type pairs)
     std::vector<long> h_cal_levels;       // plan: first entry of each level, then the sequential tail's end
     int cal_plan_key[3] = {0, 0, 0};      // width, height, cfa of the plan
+    // star finder: per-tile candidate counts and slots, per-frame constants and counters, measured records
+    sgpu_host::DevBuf star_tc, star_slots, star_fp, star_out;
+    hipEvent_t star_ev[3] = {nullptr, nullptr, nullptr};   // candidates start, measure start, measure stop
+    float star_ms[2] = {0.f, 0.f};        // last call: candidate and measure kernel time
+    std::vector<std::vector<sgpu_star>> star_cand;   // last call with keep_candidates: per frame, raster order
 
     void release_all() {
         for (sgpu_host::DevBuf *b : {&fb_list, &fb_count, &counts, &scratch, &scale, &offset, &mul,
@@ -146,6 +151,7 @@ struct sgpu_context {
                                      &dft_frames, &rl_u, &rl_e, &rl_f, &rl_r, &rl_w, &rl_taps, &rl_small,
                                      &rl_io, &rl_reg, &rl_gxy, &rlf_t1, &rlf_t2, &rlf_ka, &rlf_kb, &rlf_kt, &rlf_tw1, &rlf_tw2, &dm_ws, &dm_mm, &dm_io, &ns_state, &ns_hist, &ns_part, &ns_io, &bn_rows, &qe_buf, &qe_part, &qe_io, &onorm, &ov_ws, &ov_tab,
                                      &fb2_list, &fb2_count, &wz_ws, &wz_cnt, &fe_tab, &fe_dt, &cfa_tmp, &cstripe, &warp_ws, &cal_rows, &cal_k, &cal_cnt, &cal_plan,
+                                     &star_tc, &star_slots, &star_fp, &star_out,
                                      &seq_in[0], &seq_in[1], &seq_out, &seq_lo, &seq_hi, &seq_cnt})
             b->release();
         seq_pin[0].release();

@@ -6,6 +6,10 @@ C-ABI.
                               square selection, as Siril computes them
   * `set_shifts` / `translation_from_H` / `H_from_translation`
                             -- io/sequence.c:1863-1868, registration.c:301-313
+  * `find_stars` / `match_stars` / `register_stars` / `run_register`
+                            -- star detection and star-based global
+                              registration (modelled on Siril's
+                              star finder and matcher, parity unpinned)
 """
 from __future__ import annotations
 
@@ -327,3 +331,349 @@ def warp_frames(frames, Hs, ref_index: int, interpolation: int = OPENCV_LANCZOS4
                                         int(ref_index), int(interpolation), int(bool(clamp))),
           "sgpu_warp_frames_device")
     return out
+
+
+# ---- star detection and star-based global registration ---------------------
+# sgpu_star (include/sirilgpu.h)
+STAR_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("flux", "f8"), ("amp", "f8"), ("fwhm_major", "f8"),
+                       ("fwhm_minor", "f8"), ("roundness", "f8"), ("px", "i4"), ("py", "i4"), ("npix", "i4"),
+                       ("ext", "i4", 4), ("reject", "i4")])
+MODELS = {"shift": 0, "similarity": 1, "affine": 2, "homography": 3}
+STAR_PARAMS = ("ksigma", "radius", "smooth_sigma", "roundness_min", "min_amp", "cut", "min_fwhm", "sat", "max_stars")
+MATCH_PARAMS = ("nbright", "tri_tol", "match_radius", "min_pairs", "model")
+
+
+def star_params(**params):
+    """sgpu_star_params with the defaults of DESIGN.md 6f, overridden by `params`."""
+    from ._lib import StarParams
+    p = StarParams()
+    lib().sgpu_star_default_params(C.byref(p))
+    for k, v in params.items():
+        if k not in STAR_PARAMS + ("keep_candidates",):
+            raise TypeError(f"find_stars: unknown parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def match_params(**params):
+    """sgpu_match_params with its defaults, overridden by `params` (model by name or number)."""
+    from ._lib import MatchParams
+    p = MatchParams()
+    lib().sgpu_match_default_params(C.byref(p))
+    for k, v in params.items():
+        if k not in MATCH_PARAMS:
+            raise TypeError(f"match_stars: unknown parameter {k}")
+        setattr(p, k, MODELS[v] if k == "model" and isinstance(v, str) else v)
+    return p
+
+
+def star_smooth_table(sigma: float) -> np.ndarray:
+    """The normalised float32 smoothing table of find_stars, 2 * ceil(3 sigma) + 1 taps."""
+    tab = np.zeros(13, np.float32)
+    taps = C.c_int(0)
+    check(lib().sgpu_star_smooth_table(float(sigma), tab.ctypes.data_as(C.c_void_p), C.byref(taps)),
+          "sgpu_star_smooth_table")
+    return tab[:taps.value].copy()
+
+
+def frame_background(frames, ctx):
+    """(bg, noise) per frame as find_stars defaults them: the median of the
+    normalisation statistics and the background noise, in sample units."""
+    from . import normalization as Nm
+    fr = frames.contiguous()
+    return Nm.norm_stats_device(ctx, fr, lite=True).median, Nm.bgnoise(ctx, fr)
+
+
+def find_stars(frames, ctx=None, bg=None, noise=None, details=None, **params):
+    """Stars of every frame of a CUDA tensor [N, H, W] (float32, or int16 /
+    uint16 storage of WORD samples; the rows may be a window of larger
+    frames): one STAR_DTYPE array per frame, brightest first, coordinates in
+    memory order.  bg / noise: per-frame background and noise in sample units
+    (default: frame_background).  params: ksigma, radius, smooth_sigma,
+    roundness_min, min_amp, cut, min_fwhm, sat, max_stars (DESIGN.md 6f;
+    modelled on Siril's star finder, parity unpinned).  `details`: a dict that
+    receives ncandidates, kernel_ms (candidate pass, measurement) and
+    candidates (every measured candidate per frame, raster order, with its
+    reject code)."""
+    import torch
+    from .stacking import default_context
+    ctx = ctx or default_context()
+    if frames.dim() != 3 or not frames.is_cuda or frames.stride(2) != 1 or \
+            not (frames.dtype == torch.float32 or _is16(frames)):
+        raise TypeError("frames must be a CUDA tensor [N, H, W], float32 or 16-bit, with unit column stride")
+    n, h, w = frames.shape
+    if bg is None or noise is None:
+        b0, n0 = frame_background(frames, ctx)
+        bg = b0 if bg is None else bg
+        noise = n0 if noise is None else noise
+    bg = np.ascontiguousarray(np.broadcast_to(np.asarray(bg, np.float64), (n,)))
+    noise = np.ascontiguousarray(np.broadcast_to(np.asarray(noise, np.float64), (n,)))
+    p = star_params(keep_candidates=int(details is not None), **params)
+    ms = max(int(p.max_stars), 1)
+    stars = np.zeros((n, ms), STAR_DTYPE)
+    ns = np.zeros(n, np.int32)
+    nc = np.zeros(n, np.int64)
+    ctx.set_stream(torch.cuda.current_stream(frames.device).cuda_stream)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib().sgpu_find_stars_device(ctx.h, C.c_void_p(frames.data_ptr()), frames.element_size(), n, w, h,
+                                       frames.stride(1), frames.stride(0), vp(bg), vp(noise), C.byref(p), vp(stars),
+                                       vp(ns), vp(nc)), "sgpu_find_stars_device")
+    if details is not None:
+        details["ncandidates"] = nc
+        details["kernel_ms"] = star_last_kernel_ms(ctx)
+        cands = []
+        for f in range(n):
+            cnt = C.c_long(0)
+            check(lib().sgpu_star_last_candidates(ctx.h, f, None, 0, C.byref(cnt)), "sgpu_star_last_candidates")
+            a = np.zeros(cnt.value, STAR_DTYPE)
+            if cnt.value:
+                check(lib().sgpu_star_last_candidates(ctx.h, f, vp(a), cnt.value, C.byref(cnt)),
+                      "sgpu_star_last_candidates")
+            cands.append(a)
+        details["candidates"] = cands
+    return [stars[f, :ns[f]].copy() for f in range(n)]
+
+
+def star_last_kernel_ms(ctx) -> tuple:
+    """(candidate pass, measurement): device milliseconds of ctx's last find_stars call."""
+    kms = (C.c_float * 2)()
+    check(lib().sgpu_star_last_kernel_ms(ctx.h, kms), "sgpu_star_last_kernel_ms")
+    return float(kms[0]), float(kms[1])
+
+
+def _top_down_xy(stars, height: int) -> np.ndarray:
+    """[n, 2] float64 top-down coordinates of a STAR_DTYPE array (memory-order
+    y flipped), or of an [n, 2] array that already is top-down."""
+    if isinstance(stars, np.ndarray) and stars.dtype.names:
+        return np.ascontiguousarray(np.stack([stars["x"], (height - 1) - stars["y"]], 1), np.float64)
+    return np.ascontiguousarray(np.asarray(stars, np.float64).reshape(-1, 2))
+
+
+def match_stars(ref, img, width: int, height: int, **params):
+    """Match the star list `img` of a frame to `ref` (find_stars arrays, or
+    [n, 2] top-down coordinates; brightest first) and fit the transform
+    (model "shift", "similarity", "affine" or "homography") that maps frame
+    pixels to reference pixels in Siril's top-down convention, h22 = 1.
+    Returns (H [3, 3], pairs [npairs, 2] of (img, ref) indices, registered);
+    a frame that is not registered has H all zeros."""
+    r, m = _top_down_xy(ref, height), _top_down_xy(img, height)
+    p = match_params(**params)
+    H = np.zeros(9, np.float64)
+    pairs = np.zeros((max(1, min(len(r), len(m))), 2), np.int32)
+    npairs = C.c_int(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    code = lib().sgpu_match_stars(vp(r), len(r), vp(m), len(m), int(width), int(height), C.byref(p), vp(H),
+                                  C.byref(npairs), vp(pairs))
+    if code not in (0, 1):
+        check(code, "sgpu_match_stars")
+    return H.reshape(3, 3), pairs[:npairs.value].copy(), code == 0
+
+
+def register_stars(frames, ref_index: int, ctx=None, model="homography", bg=None, noise=None, **params):
+    """Star-based global registration of a CUDA tensor [N, H, W] against frame
+    ref_index.  Returns (Hs [N, 3, 3], info): Hs go straight into warp_frames
+    (Hs[ref_index] is the identity; a frame that did not register has the
+    null homography and must be left out).  info: per-frame nstars, npairs,
+    registered, fwhm (mean of sqrt(fwhm_major * fwhm_minor) over the frame's
+    stars), wfwhm (fwhm * (nstars_ref - min_pairs) / (npairs - min_pairs), 0
+    when undefined; modelled on Siril's weighted FWHM, parity unpinned),
+    roundness (mean), bkg, and the star lists."""
+    from .stacking import default_context
+    ctx = ctx or default_context()
+    sp = {k: v for k, v in params.items() if k in STAR_PARAMS}
+    mp = {k: v for k, v in params.items() if k in MATCH_PARAMS}
+    unknown = set(params) - set(sp) - set(mp)
+    if unknown:
+        raise TypeError(f"register_stars: unknown parameters {sorted(unknown)}")
+    n, h, w = frames.shape
+    if bg is None or noise is None:
+        b0, n0 = frame_background(frames, ctx)
+        bg = b0 if bg is None else bg
+        noise = n0 if noise is None else noise
+    stars = find_stars(frames, ctx=ctx, bg=bg, noise=noise, **sp)
+    min_pairs = int(match_params(model=model, **mp).min_pairs)
+    Hs = np.zeros((n, 3, 3), np.float64)
+    npairs = np.zeros(n, np.int32)
+    reg = np.zeros(n, bool)
+    for f in range(n):
+        if f == ref_index:
+            Hs[f], npairs[f], reg[f] = np.eye(3), len(stars[f]), True
+            continue
+        Hs[f], pr, reg[f] = match_stars(stars[ref_index], stars[f], w, h, model=model, **mp)
+        npairs[f] = len(pr)
+    mean = lambda v: float(v.mean()) if len(v) else 0.0
+    fwhm = np.array([mean(np.sqrt(s["fwhm_major"] * s["fwhm_minor"])) for s in stars])
+    nref = len(stars[ref_index])
+    wfwhm = np.array([fwhm[f] * (nref - min_pairs) / (npairs[f] - min_pairs)
+                      if reg[f] and npairs[f] > min_pairs and nref > min_pairs else 0.0 for f in range(n)])
+    info = dict(nstars=np.array([len(s) for s in stars], np.int32), npairs=npairs, registered=reg, fwhm=fwhm,
+                wfwhm=wfwhm, roundness=np.array([mean(s["roundness"]) for s in stars]),
+                bkg=np.broadcast_to(np.asarray(bg, np.float64), (n,)).copy(), stars=stars)
+    return Hs, info
+
+
+# ---- the `register` command --------------------------------------------------
+INTERPOLATIONS = {"nearest": OPENCV_NEAREST, "ne": OPENCV_NEAREST, "linear": OPENCV_LINEAR, "li": OPENCV_LINEAR,
+                  "cubic": OPENCV_CUBIC, "cu": OPENCV_CUBIC, "area": OPENCV_AREA, "ar": OPENCV_AREA,
+                  "lanczos4": OPENCV_LANCZOS4, "la": OPENCV_LANCZOS4}
+
+
+class RegisterCommand:
+    def __init__(self, seq: str):
+        self.seq = seq
+        self.layer = 0
+        self.transf = "homography"
+        self.minpairs = 10
+        self.maxstars = 2000
+        self.noout = False
+        self.interp = OPENCV_LANCZOS4
+        self.clamp = True
+        self.prefix = "r_"
+
+
+def parse_register_command(words) -> RegisterCommand:
+    """`register <seq> [-layer=] [-transf=shift|similarity|affine|homography]
+    [-minpairs=] [-maxstars=] [-noout] [-interp=ne|li|cu|ar|la] [-noclamp]
+    [-prefix=r_]`."""
+    words = list(words)
+    if words and words[0] == "register":
+        words = words[1:]
+    if not words or words[0].startswith("-"):
+        raise ValueError("register needs a sequence name")
+    cmd = RegisterCommand(words[0])
+    for o in words[1:]:
+        if o.startswith("-layer="):
+            cmd.layer = int(o[7:])
+            if cmd.layer < 0:
+                raise ValueError("-layer= must not be negative")
+        elif o.startswith("-transf="):
+            if o[8:] not in MODELS:
+                raise ValueError(f"Unknown transformation type {o[8:]}, aborting.")
+            cmd.transf = o[8:]
+        elif o.startswith("-minpairs="):
+            cmd.minpairs = int(o[10:])
+            if cmd.minpairs < 1:
+                raise ValueError("-minpairs= must be at least 1")
+        elif o.startswith("-maxstars="):
+            cmd.maxstars = int(o[10:])
+            if not 1 <= cmd.maxstars <= 2000:
+                raise ValueError("-maxstars= must be between 1 and 2000")
+        elif o == "-noout":
+            cmd.noout = True
+        elif o.startswith("-interp="):
+            if o[8:] not in INTERPOLATIONS:
+                raise ValueError(f"Unknown interpolation {o[8:]}, aborting.")
+            cmd.interp = INTERPOLATIONS[o[8:]]
+        elif o == "-noclamp":
+            cmd.clamp = False
+        elif o.startswith("-prefix="):
+            cmd.prefix = o[8:]
+            if not cmd.prefix:
+                raise ValueError("Missing prefix after -prefix=")
+        else:
+            raise ValueError(f"Unexpected argument to register `{o}', aborting.")
+    return cmd
+
+
+def _seq_reference(path: str) -> int:
+    """reference_image of the S line (-1: none chosen)."""
+    with open(path) as f:
+        for line in f:
+            if line.startswith("S "):
+                rest = line[2:].strip()
+                rest = rest[1:].split("'", 1)[1].split() if rest.startswith("'") else rest.split()[1:]
+                return int(rest[4])
+    raise ValueError(f"{path}: no S line")
+
+
+def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
+    """Run one `register` command line (a string or its words) on a regular
+    FITS sequence: finds the stars of every frame (layer -layer= of RGB
+    frames), matches them against the reference frame's, rewrites <seq>.seq
+    with the homographies and the registration values (frames that did not
+    register are deselected) and, unless -noout, writes the warped frames as
+    32-bit <prefix><name>NNNNN.fit (the registered frames, renumbered
+    consecutively) with their .seq (identity H).  Stacking a
+    -noout sequence whose H are more than translations needs that output:
+    the .seq reader takes h02 / h12 only.  Returns (path of the .seq written
+    last, Hs, info)."""
+    import os
+    import torch
+    from .calibration import INV_USHRT_MAX, _read_seq
+    from .sequence import frame_name, read_fits, write_fits, write_seq
+    from .stacking import Context
+    cmd = parse_register_command(line.split() if isinstance(line, str) else line)
+    seq = cmd.seq if cmd.seq.endswith(".seq") else cmd.seq + ".seq"
+    d = os.path.dirname(os.path.abspath(seq))
+    name, fixed, nums = _read_seq(seq)
+    if nums != list(range(nums[0], nums[0] + len(nums))):
+        raise ValueError("register needs consecutively numbered images")
+    n = len(nums)
+    ref_index = _seq_reference(seq)
+    ref_index = ref_index if 0 <= ref_index < n else 0
+    ctx = ctx or Context(0)
+    dev = torch.device("cuda", ctx.device)
+
+    def read(num):
+        a = read_fits(os.path.join(d, frame_name(name, num, fixed)))
+        if a.ndim == 3:
+            if cmd.layer >= a.shape[0]:
+                raise ValueError("-layer= is outside the frames' layers")
+            a = a[cmd.layer]
+        elif cmd.layer:
+            raise ValueError("-layer= is outside the frames' layers")
+        return np.ascontiguousarray(a)
+
+    def upload(host):
+        return torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(dev)
+
+    first = read(nums[0])
+    h, w = first.shape
+    batch = max(1, int(max_batch_bytes // (h * w * 4)))
+    stars, bkg = [], []
+    for b0 in range(0, n, batch):
+        t = upload(np.stack([read(num) for num in nums[b0:b0 + batch]]))
+        bg, noise = frame_background(t, ctx)
+        stars.extend(find_stars(t, ctx=ctx, bg=bg, noise=noise, max_stars=cmd.maxstars))
+        bkg.extend(bg)
+    Hs = np.zeros((n, 3, 3))
+    npairs = np.zeros(n, np.int32)
+    reg = np.zeros(n, bool)
+    for f in range(n):
+        if f == ref_index:
+            Hs[f], npairs[f], reg[f] = np.eye(3), len(stars[f]), True
+            continue
+        Hs[f], pr, reg[f] = match_stars(stars[ref_index], stars[f], w, h, model=cmd.transf, min_pairs=cmd.minpairs)
+        npairs[f] = len(pr)
+    mean = lambda v: float(v.mean()) if len(v) else 0.0
+    fwhm = [mean(np.sqrt(s["fwhm_major"] * s["fwhm_minor"])) for s in stars]
+    nref = len(stars[ref_index])
+    wfwhm = [fwhm[f] * (nref - cmd.minpairs) / (npairs[f] - cmd.minpairs)
+             if reg[f] and npairs[f] > cmd.minpairs and nref > cmd.minpairs else 0.0 for f in range(n)]
+    info = dict(nstars=np.array([len(s) for s in stars], np.int32), npairs=npairs, registered=reg,
+                fwhm=np.array(fwhm), wfwhm=np.array(wfwhm), roundness=np.array([mean(s["roundness"]) for s in stars]),
+                bkg=np.array(bkg, np.float64), stars=stars)
+    regdata = dict(fwhm=info["fwhm"], wfwhm=info["wfwhm"], roundness=info["roundness"], bkg=info["bkg"],
+                   nstars=info["nstars"])
+    write_seq(seq, name, n, beg=nums[0], fixed=fixed, reference=ref_index, included=reg, homographies=Hs,
+              reg_layer=cmd.layer, **regdata)
+    if cmd.noout:
+        return seq, Hs, info
+    good = [f for f in range(n) if reg[f]]
+    per = max(1, batch // 2 - 1)                      # input and output frames, and the reference frame's slot
+    for b0 in range(0, len(good), per):
+        part = good[b0:b0 + per]
+        idx = part if ref_index in part else part + [ref_index]
+        t = upload(np.stack([read(nums[f]) for f in idx]))
+        res = warp_frames(t, Hs[idx], idx.index(ref_index), cmd.interp, cmd.clamp, ctx=ctx).cpu().numpy()
+        for j, f in enumerate(part):
+            a = res[j]
+            if a.dtype != np.float32:                 # WORD frames: [0, 1] units, as 32-bit FITS hold them
+                a = a.view(np.uint16).astype(np.float32) * np.float32(INV_USHRT_MAX)
+            write_fits(os.path.join(d, frame_name(cmd.prefix + name, nums[0] + b0 + j, fixed)), a)
+    # the new sequence holds the registered frames only, renumbered from the first image number
+    out_seq = os.path.join(d, cmd.prefix + name + ".seq")
+    write_seq(out_seq, cmd.prefix + name, len(good), beg=nums[0], fixed=fixed, reference=good.index(ref_index),
+              homographies=np.tile(np.eye(3), (len(good), 1, 1)), reg_layer=cmd.layer,
+              **{k: v[good] for k, v in regdata.items()})
+    return out_seq, Hs, info

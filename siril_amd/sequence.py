@@ -175,13 +175,15 @@ def read_frame_rows(path: str, frame: int, layer: int = 0, row0: int = 0, nrows:
 def write_seq(path: str, name: str, number: int, beg: int = 1, fixed: int = 5, reference: int = 0,
               included: Optional[Sequence[bool]] = None, shifts: Optional[Sequence[tuple]] = None,
               kind: Optional[str] = None, nb_layers: int = 1, reg_layer: int = 0, fwhm=None, quality=None,
-              wfwhm=None, roundness=None, bkg=None, nstars=None):
+              wfwhm=None, roundness=None, bkg=None, nstars=None, homographies=None):
     """Sequence file, version 4 (io/seqfile.c:730-910): S, T (kind "S" SER,
     "F" FITSEQ; None regular FITS), L and I lines, and R<reg_layer> lines with
     the shift-only homography when `shifts` (dx, dy) is given (h02 = dx,
     h12 = -dy, registration.c:306-313) and optional per-frame registration
     values (fwhm, weighted fwhm, roundness, quality, background, stars;
-    seqfile.c:814-829)."""
+    seqfile.c:814-829).  `homographies` ([number, 3, 3], top-down as Siril
+    stores them) writes all nine entries of every H instead; the null
+    homography (all zeros) marks a frame that is not registered."""
     inc = list(included) if included is not None else [True] * number
     lines = ["#Siril sequence file. Contains list of images, selection, registration data and statistics",
              "#S 'sequence_name' start_index nb_images nb_selected fixed_len reference_image version"
@@ -192,12 +194,20 @@ def write_seq(path: str, name: str, number: int, beg: int = 1, fixed: int = 5, r
     lines.append(f"L {nb_layers}")
     for i in range(number):
         lines.append(f"I {(beg + i) if not kind else i} {int(bool(inc[i]))}")
-    if shifts is not None:
-        for i, (dx, dy) in enumerate(shifts):
+    if homographies is not None:
+        if shifts is not None:
+            raise ValueError("write_seq takes shifts or homographies, not both")
+        hs = np.asarray(homographies, np.float64).reshape(number, 9)
+    if shifts is not None or homographies is not None:
+        for i in range(number if homographies is not None else len(shifts)):
             v = [0 if a is None else a[i] for a in (fwhm, wfwhm, roundness, quality, bkg)]
             ns = 0 if nstars is None else int(nstars[i])
-            lines.append(f"R{reg_layer} {v[0]:.9g} {v[1]:.9g} {v[2]:.9g} {v[3]:.17g} {v[4]:.9g} {ns} "
-                         f"H 1 0 {dx:.17g} 0 1 {-dy:.17g} 0 0 1")
+            if homographies is not None:
+                h = " ".join(f"{a:.17g}" for a in hs[i])
+            else:
+                dx, dy = shifts[i]
+                h = f"1 0 {dx:.17g} 0 1 {-dy:.17g} 0 0 1"
+            lines.append(f"R{reg_layer} {v[0]:.9g} {v[1]:.9g} {v[2]:.9g} {v[3]:.17g} {v[4]:.9g} {ns} H {h}")
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
 
