@@ -564,7 +564,9 @@ int sgpu_calibrate_frames_device(sgpu_context *ctx, const void *d_in, float *d_o
 
 /* Arithmetic: the specification in DESIGN.md 6f, restated in
  * tests/star_ref.py; modelled on Siril's star_finder.c and matching/, with
- * image moments in place of the PSF fit.  Parity with Siril is unpinned. */
+ * image moments as the finder's measurement; the Gaussian / Moffat PSF fit
+ * is a separate, optional stage (sgpu_fit_stars_device).
+ * Parity with Siril is unpinned. */
 
 #define SGPU_NOT_REGISTERED 1   /* sgpu_match_stars: too few pairs; H is all zeros (the null homography) */
 
@@ -640,6 +642,57 @@ int sgpu_star_last_kernel_ms(sgpu_context *ctx, float ms[2]);
  * and *npairs the pairs found.  Deterministic.  Host only. */
 int sgpu_match_stars(const double *ref_xy, int nref, const double *img_xy, int nimg, int width, int height,
 		const sgpu_match_params *params, double H[9], int *npairs, int *pairs);
+
+/* PSF fit of found stars (restated in tests/psf_ref.py):
+ * Levenberg-Marquardt in double on the raw (2b+1)^2 box of every star,
+ * b = min(radius, max(ext) + 2), of f = B + A exp(-Q/2) (Gaussian) or
+ * f = B + A (1 + Q)^-beta (Moffat), Q = a u^2 + 2b uv + c v^2 about the fitted
+ * centre.  Modelled on Siril's psf.c; parity with Siril is unpinned. */
+#define SGPU_PSF_GAUSSIAN 0
+#define SGPU_PSF_MOFFAT   1
+
+typedef struct sgpu_psf_params {
+	double beta;            /* Moffat: fixed exponent, 0.5..10; <= 0: fitted, starting at 2.5 (0) */
+	double min_fwhm;        /* pixels (1.0) */
+	double roundness_min;   /* (0.5) */
+	double sat;             /* a sample >= sat is left out of the fit (+inf) */
+	int profile;            /* SGPU_PSF_GAUSSIAN / SGPU_PSF_MOFFAT (Gaussian) */
+	int radius;             /* largest box half-size, 1..16 (10) */
+	int max_iter;           /* accepted steps (50) */
+	int reserved;
+} sgpu_psf_params;
+
+typedef struct sgpu_psf {
+	double x, y;            /* fitted centre, memory order, pixel centres at integers */
+	double bkg, amp;        /* B, A */
+	double fwhm_major, fwhm_minor, roundness;
+	double angle;           /* direction of the major axis, degrees in (-90, 90], memory order */
+	double beta;            /* Moffat exponent (fitted or fixed); 0 for a Gaussian */
+	double rmse;            /* sqrt(chi^2 / (nused - parameters)) */
+	double a, b, c;         /* the quadratic form */
+	int nused;              /* samples in the fit */
+	int iterations;         /* accepted steps */
+	int status;             /* 0 fitted; 1 iteration cap, 2 damping overflow, 3 nothing fitted (non-finite
+	                           sample, too few samples, unusable start), 4 centre left the box core,
+	                           5 fwhm out of range, 6 roundness */
+	int reserved;
+} sgpu_psf;
+
+/* The defaults above. */
+void sgpu_psf_default_params(sgpu_psf_params *p);
+/* Fit every star of nframes device frames; frames, bg, stars, nstars and
+ * max_stars as sgpu_find_stars_device takes and returns them (the fields read
+ * are px, py, ext, amp, x, y, fwhm_major, fwhm_minor).  psf: nframes x
+ * max_stars records, psf[f * max_stars + s] for stars[f * max_stars + s]; it
+ * is filled for every status with the last accepted point.  The record of a
+ * star does not depend on the other stars, their order or their number.  A
+ * bad parameter, or a star whose box leaves the frame, returns
+ * SGPU_BAD_ARGUMENT; zero stars is not an error.  Synchronous. */
+int sgpu_fit_stars_device(sgpu_context *ctx, const void *d_frames, int elem_size, int nframes, int width,
+		int height, long row_stride, long frame_stride, const double *bg, const sgpu_star *stars,
+		const int *nstars, int max_stars, const sgpu_psf_params *params, sgpu_psf *psf);
+/* Device time of the fit kernel of the last sgpu_fit_stars_device call, milliseconds. */
+int sgpu_psf_last_kernel_ms(sgpu_context *ctx, float *ms);
 
 /* ---- CFA helpers -------------------------------------- */
 

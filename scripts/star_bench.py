@@ -6,7 +6,14 @@ and the host sort), the candidate and measure kernels on their own
 (sgpu_star_last_kernel_ms), the call with bg / noise defaulted (adds the
 median and bgnoise passes), and the neighbouring single-pass frame kernels
 quality_estimate and bgnoise in the same session.  The one-read HBM floor is
-the frame's bytes at 8 TB/s."""
+the frame's bytes at 8 TB/s.
+
+`python scripts/star_bench.py --psf=gaussian|moffat [out.json]`
+(profiles/star_psf_6000x4000.json) times the PSF fit of the found stars
+instead: the fit kernel per frame by HIP events
+(sgpu_psf_last_kernel_ms) beside the candidate pass and the moment measurement
+of the same session, the whole fit_stars call, the mean of accepted
+iterations per star and the statuses.  --psf=moffat fits beta as well."""
 import json
 import os
 import statistics
@@ -20,6 +27,10 @@ sys.path.insert(0, ROOT)
 from siril_amd import normalization as Nm, registration as Rg, synth  # noqa: E402
 from siril_amd.stacking import Context  # noqa: E402
 
+ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
+PSF = ([a[6:] for a in sys.argv[1:] if a.startswith("--psf=")] or [None])[0]
+if PSF not in (None, "gaussian", "moffat") or any(a.startswith("--") and not a.startswith("--psf=") for a in sys.argv[1:]):
+    sys.exit("usage: star_bench.py [--psf=gaussian|moffat] [out.json]")
 W, H, N = 6000, 4000, 4
 WARM, STEPS = 3, 15
 BG, NOISE = 0.05, 0.002
@@ -71,6 +82,25 @@ for name in ("float32", "word"):
     stars = Rg.find_stars(d, ctx=ctx, bg=bg, noise=noise, details=det)
     c["stars_per_frame"] = [len(s) for s in stars]
     c["candidates_per_frame"] = [int(v) for v in det["ncandidates"]]
+    if PSF:
+        fms = []
+
+        def fit():
+            fit.out = Rg.fit_stars(d, stars, ctx=ctx, bg=bg, profile=PSF)
+            fms.append(Rg.psf_last_kernel_ms(ctx))
+
+        c["fit_stars_per_frame"] = timed(fit)
+        q = np.concatenate(fit.out)
+        c["profile"] = PSF
+        c["fit_kernel_ms"] = round(float(np.median(np.array(fms[WARM:]) / N)), 4)
+        c["fit_kernel_us_per_star"] = round(c["fit_kernel_ms"] * N * 1e3 / len(q), 4)
+        c["mean_accepted_iterations"] = round(float(q["iterations"].mean()), 2)
+        c["mean_samples"] = round(float(q["nused"].mean()), 1)
+        c["status_counts"] = [int(v) for v in np.bincount(q["status"], minlength=7)]
+        c["fit_over_candidates"] = round(c["fit_kernel_ms"] / c["candidates_kernel_ms"], 2)
+        res["cases"][name] = c
+        print(name, json.dumps(c), flush=True)
+        continue
     c["find_stars_default_background_per_frame"] = timed(lambda: Rg.find_stars(d, ctx=ctx))
     c["quality_estimate_per_frame"] = timed(lambda: Rg.quality_estimate(d, ctx))
     c["bgnoise_per_frame"] = timed(lambda: Nm.bgnoise(ctx, d))
@@ -79,6 +109,6 @@ for name in ("float32", "word"):
     res["cases"][name] = c
     print(name, json.dumps(c), flush=True)
 
-json.dump(res, open(sys.argv[1] if len(sys.argv) > 1 else "star_bench.json", "w"), indent=1)
+json.dump(res, open(ARGS[0] if ARGS else "star_bench.json", "w"), indent=1)
 ctx.close()
 print("done", flush=True)

@@ -49,6 +49,7 @@ EXPORTS = (
     "sgpu_cosmetic_correction_device", "sgpu_dark_optimize_device", "sgpu_calibrate_frames_device",
     "sgpu_star_default_params", "sgpu_match_default_params", "sgpu_star_smooth_table", "sgpu_find_stars_device",
     "sgpu_star_last_candidates", "sgpu_star_last_kernel_ms", "sgpu_match_stars",
+    "sgpu_psf_default_params", "sgpu_fit_stars_device", "sgpu_psf_last_kernel_ms",
 )
 
 SGPU_OK = 0
@@ -88,6 +89,12 @@ class StarParams(C.Structure):
     _fields_ = [(f, C.c_double) for f in ("ksigma", "smooth_sigma", "roundness_min", "min_amp", "cut", "min_fwhm",
                                           "sat")] + \
         [(f, C.c_int) for f in ("radius", "max_stars", "keep_candidates", "reserved")]
+
+
+class PsfParams(C.Structure):
+    """sgpu_psf_params (include/sirilgpu.h)."""
+    _fields_ = [(f, C.c_double) for f in ("beta", "min_fwhm", "roundness_min", "sat")] + \
+        [(f, C.c_int) for f in ("profile", "radius", "max_iter", "reserved")]
 
 
 class MatchParams(C.Structure):
@@ -364,6 +371,13 @@ def lib():
         L.sgpu_star_last_kernel_ms.argtypes = [vp, C.POINTER(f)]
         L.sgpu_match_stars.restype = i
         L.sgpu_match_stars.argtypes = [vp, i, vp, i, i, i, C.POINTER(MatchParams), vp, pi, vp]
+        L.sgpu_psf_default_params.restype = None
+        L.sgpu_psf_default_params.argtypes = [C.POINTER(PsfParams)]
+        L.sgpu_fit_stars_device.restype = i
+        L.sgpu_fit_stars_device.argtypes = [vp, vp, i, i, i, i, C.c_long, C.c_long, vp, vp, vp, i,
+                                            C.POINTER(PsfParams), vp]
+        L.sgpu_psf_last_kernel_ms.restype = i
+        L.sgpu_psf_last_kernel_ms.argtypes = [vp, C.POINTER(f)]
         L.sgpu_extract_cfa_device.restype = i
         L.sgpu_extract_cfa_device.argtypes = [vp, vp, i, i, i, vp, i, i, vp, C.POINTER(C.c_long)]
         L.sgpu_cfa_count.restype = C.c_long

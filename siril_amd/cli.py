@@ -7,9 +7,9 @@ siril_amd/sequence.py).  Prints the output path and the rejection totals.
 <prefix><name>NNNNN.fit and the new .seq.
 
 `python -m siril_amd.cli register <seq> [-layer=N] [-transf=shift|similarity|affine|homography] [-minpairs=N]
-[-maxstars=N] [-noout] [-interp=ne|li|cu|ar|la] [-noclamp] [-prefix=r_]`: star-based global registration
-(siril_amd/registration.py); rewrites the .seq with the homographies and, unless -noout, writes the warped 32-bit
-<prefix><name>NNNNN.fit and their .seq."""
+[-maxstars=N] [-noout] [-interp=ne|li|cu|ar|la] [-noclamp] [-prefix=r_] [-psf=moments|gaussian|moffat]`: star-based
+global registration (siril_amd/registration.py); rewrites the .seq with the homographies and, unless -noout, writes
+the warped 32-bit <prefix><name>NNNNN.fit and their .seq.  -psf=gaussian|moffat measures the stars with a PSF fit."""
 import sys
 import time
 

@@ -233,6 +233,8 @@ void sgpu_release(sgpu_context *c) {
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->star_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->psf_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->own) (void)hipStreamDestroy(c->own);
     delete c;
 }

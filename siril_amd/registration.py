@@ -10,6 +10,8 @@ C-ABI.
                             -- star detection and star-based global
                               registration (modelled on Siril's
                               star finder and matcher, parity unpinned)
+  * `fit_stars`             -- Gaussian / Moffat PSF fit of the found stars
+                              (parity unpinned)
 """
 from __future__ import annotations
 
@@ -441,6 +443,105 @@ def star_last_kernel_ms(ctx) -> tuple:
     return float(kms[0]), float(kms[1])
 
 
+# ---- PSF fit of found stars ------------------------------------
+# sgpu_psf (include/sirilgpu.h)
+PSF_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("bkg", "f8"), ("amp", "f8"), ("fwhm_major", "f8"),
+                      ("fwhm_minor", "f8"), ("roundness", "f8"), ("angle", "f8"), ("beta", "f8"), ("rmse", "f8"),
+                      ("a", "f8"), ("b", "f8"), ("c", "f8"), ("nused", "i4"), ("iterations", "i4"), ("status", "i4"),
+                      ("reserved", "i4")])
+PSF_PROFILES = {"gaussian": 0, "moffat": 1}
+PSF_PARAMS = ("radius", "min_fwhm", "roundness_min", "sat", "max_iter")
+
+
+def psf_params(profile="gaussian", beta=None, **params):
+    """sgpu_psf_params with the defaults of DESIGN.md 6g, overridden by `params`
+    (profile by name or number; beta None or <= 0: fitted)."""
+    from ._lib import PsfParams
+    p = PsfParams()
+    lib().sgpu_psf_default_params(C.byref(p))
+    if isinstance(profile, str):
+        if profile not in PSF_PROFILES:
+            raise ValueError(f"fit_stars: unknown profile {profile}")
+        profile = PSF_PROFILES[profile]
+    p.profile = int(profile)
+    p.beta = 0.0 if beta is None else float(beta)
+    for k, v in params.items():
+        if k not in PSF_PARAMS:
+            raise TypeError(f"fit_stars: unknown parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def fit_stars(frames, stars, ctx=None, bg=None, profile="gaussian", beta=None, **params):
+    """Gaussian or Moffat PSF fit (modelled on Siril's PSF fit,
+    parity unpinned) of the stars find_stars returned for the CUDA tensor
+    `frames` [N, H, W]: one PSF_DTYPE array per frame, aligned with `stars`.
+    `status` 0 marks a fitted, accepted star.  bg: per-frame background
+    (default: frame_background).  profile "gaussian" or "moffat"; beta fixes
+    the Moffat exponent (None: fitted).  params: radius, min_fwhm,
+    roundness_min, sat, max_iter."""
+    import torch
+    from .stacking import default_context
+    ctx = ctx or default_context()
+    if frames.dim() != 3 or not frames.is_cuda or frames.stride(2) != 1 or \
+            not (frames.dtype == torch.float32 or _is16(frames)):
+        raise TypeError("frames must be a CUDA tensor [N, H, W], float32 or 16-bit, with unit column stride")
+    n, h, w = frames.shape
+    if len(stars) != n:
+        raise ValueError("fit_stars needs one star list per frame")
+    if bg is None:
+        bg = frame_background(frames, ctx)[0]
+    bg = np.ascontiguousarray(np.broadcast_to(np.asarray(bg, np.float64), (n,)))
+    p = psf_params(profile, beta, **params)
+    ns = np.array([len(s) for s in stars], np.int32)
+    ms = max(int(ns.max()), 1)
+    flat = np.zeros((n, ms), STAR_DTYPE)
+    for f in range(n):
+        flat[f, :ns[f]] = stars[f]
+    psf = np.zeros((n, ms), PSF_DTYPE)
+    ctx.set_stream(torch.cuda.current_stream(frames.device).cuda_stream)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib().sgpu_fit_stars_device(ctx.h, C.c_void_p(frames.data_ptr()), frames.element_size(), n, w, h,
+                                      frames.stride(1), frames.stride(0), vp(bg), vp(flat), vp(ns), ms, C.byref(p),
+                                      vp(psf)), "sgpu_fit_stars_device")
+    return [psf[f, :ns[f]].copy() for f in range(n)]
+
+
+def psf_last_kernel_ms(ctx) -> float:
+    """Device milliseconds of the fit kernel of ctx's last fit_stars call."""
+    ms = C.c_float(0)
+    check(lib().sgpu_psf_last_kernel_ms(ctx.h, C.byref(ms)), "sgpu_psf_last_kernel_ms")
+    return float(ms.value)
+
+
+def _fitted_stars(stars, psf):
+    """The stars whose fit has status 0, in the same (flux) order, with the
+    fitted centre, widths and roundness in place of the moments' (PSF records
+    of the same stars as the second list)."""
+    out, kept = [], []
+    for s, q in zip(stars, psf):
+        m = q["status"] == 0
+        s, q = s[m].copy(), q[m]
+        for k in ("x", "y", "fwhm_major", "fwhm_minor", "roundness"):
+            s[k] = q[k]
+        out.append(s)
+        kept.append(q)
+    return out, kept
+
+
+def _registration_values(stars, ref_index: int, npairs, reg, min_pairs: int):
+    """(fwhm, wfwhm, roundness) of every frame from its star list: the mean of
+    sqrt(fwhm_major * fwhm_minor), that value weighted by (nstars_ref -
+    min_pairs) / (npairs - min_pairs) (0 when undefined), the mean roundness."""
+    mean = lambda v: float(v.mean()) if len(v) else 0.0
+    n = len(stars)
+    fwhm = np.array([mean(np.sqrt(s["fwhm_major"] * s["fwhm_minor"])) for s in stars])
+    nref = len(stars[ref_index])
+    wfwhm = np.array([fwhm[f] * (nref - min_pairs) / (npairs[f] - min_pairs)
+                      if reg[f] and npairs[f] > min_pairs and nref > min_pairs else 0.0 for f in range(n)])
+    return fwhm, wfwhm, np.array([mean(s["roundness"]) for s in stars])
+
+
 def _top_down_xy(stars, height: int) -> np.ndarray:
     """[n, 2] float64 top-down coordinates of a STAR_DTYPE array (memory-order
     y flipped), or of an [n, 2] array that already is top-down."""
@@ -469,7 +570,27 @@ def match_stars(ref, img, width: int, height: int, **params):
     return H.reshape(3, 3), pairs[:npairs.value].copy(), code == 0
 
 
-def register_stars(frames, ref_index: int, ctx=None, model="homography", bg=None, noise=None, **params):
+# Accepted steps the registration allows a fit.  A Moffat profile reaches a
+# Gaussian only as beta grows without limit, so on Gaussian-like stars the
+# fitted beta settles at its bound of 10, where every overshooting step is
+# rejected first and the damping has to rise again: those fits converge, but
+# need 54-93 steps on the frames of DESIGN.md 6g, more than fit_stars' default
+# of 50, which would end them with status 1 and drop the star.
+PSF_REGISTER_MAX_ITER = {"gaussian": 50, "moffat": 200}
+
+
+def _psf_stage(frames, stars, ctx, bg, psf, sp):
+    """The optional PSF stage of the registration: (stars, psf records) with
+    the stars whose fit failed dropped and the fitted values in place; the
+    finder's radius, min_fwhm, roundness_min and sat carry over to the fit."""
+    if psf not in PSF_PROFILES:
+        raise ValueError(f"register_stars: psf must be None, 'gaussian' or 'moffat', not {psf!r}")
+    fp = {k: sp[k] for k in ("radius", "min_fwhm", "roundness_min", "sat") if k in sp}
+    return _fitted_stars(stars, fit_stars(frames, stars, ctx=ctx, bg=bg, profile=psf,
+                                          max_iter=PSF_REGISTER_MAX_ITER[psf], **fp))
+
+
+def register_stars(frames, ref_index: int, ctx=None, model="homography", bg=None, noise=None, psf=None, **params):
     """Star-based global registration of a CUDA tensor [N, H, W] against frame
     ref_index.  Returns (Hs [N, 3, 3], info): Hs go straight into warp_frames
     (Hs[ref_index] is the identity; a frame that did not register has the
@@ -477,7 +598,12 @@ def register_stars(frames, ref_index: int, ctx=None, model="homography", bg=None
     registered, fwhm (mean of sqrt(fwhm_major * fwhm_minor) over the frame's
     stars), wfwhm (fwhm * (nstars_ref - min_pairs) / (npairs - min_pairs), 0
     when undefined; modelled on Siril's weighted FWHM, parity unpinned),
-    roundness (mean), bkg, and the star lists."""
+    roundness (mean), bkg, and the star lists.  psf "gaussian" or "moffat"
+    (beta fitted, up to PSF_REGISTER_MAX_ITER accepted steps) fits every star
+    (fit_stars): the stars whose fit did not end
+    with status 0 are dropped, the matcher pairs the fitted centres, fwhm /
+    wfwhm / roundness come from the fitted values, and info gains `psf`, the
+    fit records of the kept stars."""
     from .stacking import default_context
     ctx = ctx or default_context()
     sp = {k: v for k, v in params.items() if k in STAR_PARAMS}
@@ -491,6 +617,9 @@ def register_stars(frames, ref_index: int, ctx=None, model="homography", bg=None
         bg = b0 if bg is None else bg
         noise = n0 if noise is None else noise
     stars = find_stars(frames, ctx=ctx, bg=bg, noise=noise, **sp)
+    fits = None
+    if psf is not None:
+        stars, fits = _psf_stage(frames, stars, ctx, bg, psf, sp)
     min_pairs = int(match_params(model=model, **mp).min_pairs)
     Hs = np.zeros((n, 3, 3), np.float64)
     npairs = np.zeros(n, np.int32)
@@ -501,14 +630,12 @@ def register_stars(frames, ref_index: int, ctx=None, model="homography", bg=None
             continue
         Hs[f], pr, reg[f] = match_stars(stars[ref_index], stars[f], w, h, model=model, **mp)
         npairs[f] = len(pr)
-    mean = lambda v: float(v.mean()) if len(v) else 0.0
-    fwhm = np.array([mean(np.sqrt(s["fwhm_major"] * s["fwhm_minor"])) for s in stars])
-    nref = len(stars[ref_index])
-    wfwhm = np.array([fwhm[f] * (nref - min_pairs) / (npairs[f] - min_pairs)
-                      if reg[f] and npairs[f] > min_pairs and nref > min_pairs else 0.0 for f in range(n)])
+    fwhm, wfwhm, roundness = _registration_values(stars, ref_index, npairs, reg, min_pairs)
     info = dict(nstars=np.array([len(s) for s in stars], np.int32), npairs=npairs, registered=reg, fwhm=fwhm,
-                wfwhm=wfwhm, roundness=np.array([mean(s["roundness"]) for s in stars]),
+                wfwhm=wfwhm, roundness=roundness,
                 bkg=np.broadcast_to(np.asarray(bg, np.float64), (n,)).copy(), stars=stars)
+    if fits is not None:
+        info["psf"] = fits
     return Hs, info
 
 
@@ -529,12 +656,13 @@ class RegisterCommand:
         self.interp = OPENCV_LANCZOS4
         self.clamp = True
         self.prefix = "r_"
+        self.psf = "moments"
 
 
 def parse_register_command(words) -> RegisterCommand:
     """`register <seq> [-layer=] [-transf=shift|similarity|affine|homography]
     [-minpairs=] [-maxstars=] [-noout] [-interp=ne|li|cu|ar|la] [-noclamp]
-    [-prefix=r_]`."""
+    [-prefix=r_] [-psf=moments|gaussian|moffat]`."""
     words = list(words)
     if words and words[0] == "register":
         words = words[1:]
@@ -570,6 +698,10 @@ def parse_register_command(words) -> RegisterCommand:
             cmd.prefix = o[8:]
             if not cmd.prefix:
                 raise ValueError("Missing prefix after -prefix=")
+        elif o.startswith("-psf="):
+            if o[5:] != "moments" and o[5:] not in PSF_PROFILES:
+                raise ValueError(f"Unknown PSF profile {o[5:]}, aborting.")
+            cmd.psf = o[5:]
         else:
             raise ValueError(f"Unexpected argument to register `{o}', aborting.")
     return cmd
@@ -595,7 +727,8 @@ def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
     32-bit <prefix><name>NNNNN.fit (the registered frames, renumbered
     consecutively) with their .seq (identity H).  Stacking a
     -noout sequence whose H are more than translations needs that output:
-    the .seq reader takes h02 / h12 only.  Returns (path of the .seq written
+    the .seq reader takes h02 / h12 only.  -psf=gaussian|moffat fits every
+    star as register_stars(psf=) does.  Returns (path of the .seq written
     last, Hs, info)."""
     import os
     import torch
@@ -630,11 +763,15 @@ def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
     first = read(nums[0])
     h, w = first.shape
     batch = max(1, int(max_batch_bytes // (h * w * 4)))
-    stars, bkg = [], []
+    stars, bkg, fits = [], [], []
     for b0 in range(0, n, batch):
         t = upload(np.stack([read(num) for num in nums[b0:b0 + batch]]))
         bg, noise = frame_background(t, ctx)
-        stars.extend(find_stars(t, ctx=ctx, bg=bg, noise=noise, max_stars=cmd.maxstars))
+        found = find_stars(t, ctx=ctx, bg=bg, noise=noise, max_stars=cmd.maxstars)
+        if cmd.psf != "moments":
+            found, q = _psf_stage(t, found, ctx, bg, cmd.psf, {})
+            fits.extend(q)
+        stars.extend(found)
         bkg.extend(bg)
     Hs = np.zeros((n, 3, 3))
     npairs = np.zeros(n, np.int32)
@@ -645,14 +782,11 @@ def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
             continue
         Hs[f], pr, reg[f] = match_stars(stars[ref_index], stars[f], w, h, model=cmd.transf, min_pairs=cmd.minpairs)
         npairs[f] = len(pr)
-    mean = lambda v: float(v.mean()) if len(v) else 0.0
-    fwhm = [mean(np.sqrt(s["fwhm_major"] * s["fwhm_minor"])) for s in stars]
-    nref = len(stars[ref_index])
-    wfwhm = [fwhm[f] * (nref - cmd.minpairs) / (npairs[f] - cmd.minpairs)
-             if reg[f] and npairs[f] > cmd.minpairs and nref > cmd.minpairs else 0.0 for f in range(n)]
+    fwhm, wfwhm, roundness = _registration_values(stars, ref_index, npairs, reg, cmd.minpairs)
     info = dict(nstars=np.array([len(s) for s in stars], np.int32), npairs=npairs, registered=reg,
-                fwhm=np.array(fwhm), wfwhm=np.array(wfwhm), roundness=np.array([mean(s["roundness"]) for s in stars]),
-                bkg=np.array(bkg, np.float64), stars=stars)
+                fwhm=fwhm, wfwhm=wfwhm, roundness=roundness, bkg=np.array(bkg, np.float64), stars=stars)
+    if cmd.psf != "moments":
+        info["psf"] = fits
     regdata = dict(fwhm=info["fwhm"], wfwhm=info["wfwhm"], roundness=info["roundness"], bkg=info["bkg"],
                    nstars=info["nstars"])
     write_seq(seq, name, n, beg=nums[0], fixed=fixed, reference=ref_index, included=reg, homographies=Hs,
