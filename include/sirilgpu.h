@@ -228,6 +228,14 @@ int sgpu_set_input_bitpix(sgpu_context *ctx, int bitpix);
  * Synchronises the context stream. */
 long sgpu_last_exact_pixels(sgpu_context *ctx);
 
+/* Float WINSORIZED stacks of 65..128 frames (last launch of the last stack
+ * call): the rejection rounds run as a head pass of SGPU_WZ_SPLIT rounds
+ * (default 2) and two compacted tail passes over the pixels that need more.
+ * out[0] / out[1]: pixels that entered tail pass 1 / 2, summed over the
+ * launch's chunks; 0 when the split did not run.  Read on request only (no
+ * work on the stack's own path).  Synchronises the context stream. */
+int sgpu_last_wz_deferred(sgpu_context *ctx, long long out[2]);
+
 /* Float NO_REJEC mean (last launch of the last stack call, <= 2^28 pixels):
  * the number of pixels whose float mean the kernel could not prove to be
  * independent of the summation order.  The reference sums kept >= 16 samples

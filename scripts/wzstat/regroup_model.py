@@ -8,11 +8,12 @@ import ctypes as C, numpy as np, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from siril_amd import synth
 L=C.CDLL(os.environ.get('WZ_LIB', '/tmp/wz/libwz2.so'))
-n=100; h=8; w=16384
+n=int(os.environ.get('WZ_N', '100')); h=8; w=16384
+sig=float(os.environ.get('WZ_SIG', '3'))
 fr=synth.frames_numpy(n,h,w,seed=3).reshape(n,-1)
 ncol=fr.shape[1]
 out=np.zeros((ncol,20),np.int32)
-L.wz_stats2(fr.ctypes.data_as(C.c_void_p), n, C.c_longlong(ncol), C.c_float(3), C.c_float(3), out.ctypes.data_as(C.c_void_p))
+L.wz_stats2(fr.ctypes.data_as(C.c_void_p), n, C.c_longlong(ncol), C.c_float(sig), C.c_float(sig), out.ctypes.data_as(C.c_void_p))
 route=out[:,0]; rounds=out[:,1]; iters=out[:,2]; it=out[:,4:20]
 ok=route==0
 print('pixels',ncol,'route0 frac',ok.mean(),'rounds avg',rounds[ok].mean(),'iters avg',iters[ok].mean())
@@ -79,3 +80,26 @@ for B in (256,512,1024):
     print('block-level compaction every round, block %d: cost ratio %.3f'%(B, block_compact(B)/tot))
 for B in (128,192):
     print('block-level compaction every round, block %d: cost ratio %.3f'%(B, block_compact(B)/tot))
+# split rounds (SGPU_WZ_SPLIT): the loop nest for `cut` rounds, then compacted
+# passes over the pixels still going -- one tail to the end, or a compaction every `cut` rounds
+# (the last of `passes` tail passes runs to the end).  A compacted wave pays CS units to restart
+# (list, state and record reload, constants).  WZ_N / WZ_SIG in the environment: other data.
+CS=8.0
+def nest_rounds(idx, r0, r1):   # rounds [r0, r1) of the wave idx as one nest
+    c=0.0
+    for r in range(r0, min(r1, int(rounds[idx].max()))):
+        act=rounds[idx]>r
+        if act.any(): c+=CR+it[idx][act][:,r].max()
+    return c
+def split_cost(cut, passes):
+    c=sum(nest_rounds(np.arange(k*64,(k+1)*64), 0, cut) for k in range(W))
+    r0=cut
+    for ps in range(passes):
+        act=np.nonzero(rounds>r0)[0]
+        r1=16 if ps==passes-1 else r0+cut
+        for k in range(0,len(act),64): c+=CS+nest_rounds(act[k:k+64], r0, r1)
+        r0=r1
+    return c
+for cut in (1,2,3):
+    print('split: nest for %d rounds, one tail to the end: cost ratio %.3f; two tails %.3f; compaction every %d rounds (6 passes) %.3f; deferred after the cut %.3f'
+          %(cut, split_cost(cut,1)/tot, split_cost(cut,2)/tot, cut, split_cost(cut,6)/tot, float((rounds>cut).mean())))

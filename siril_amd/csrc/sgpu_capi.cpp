@@ -308,6 +308,18 @@ long sgpu_last_exact_pixels(sgpu_context *c) {
     return n;
 }
 
+int sgpu_last_wz_deferred(sgpu_context *c, long long out[2]) {
+    if (!c || !out) return fail(SGPU_BAD_ARGUMENT, "null argument");
+    out[0] = out[1] = 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!c->wz_cnt.p) return SGPU_OK;
+    int t[2] = {0, 0};
+    HIP_TRY(hipMemcpy(t, (int *)c->wz_cnt.p + sgpu::kWzDefOff, sizeof t, hipMemcpyDeviceToHost));
+    out[0] = t[0];
+    out[1] = t[1];
+    return SGPU_OK;
+}
+
 long sgpu_last_order_sensitive(sgpu_context *c, int *idx, long cap) {
     if (!c) return fail(SGPU_BAD_ARGUMENT, "null context");
     if (hipStreamSynchronize(c->stream) != hipSuccess) return SGPU_NO_DEVICE;
@@ -481,7 +493,8 @@ int run_launch_body(sgpu_context *c, KParams k, bool has_shift) {
     k.fb_list = (int *)c->fb_list.p;
     k.fb_count = (int *)c->fb_count.p;
     HIP_TRY(hipMemsetAsync(k.fb_count, 0, sizeof(int), s));
-    if (c->wz_cnt.p) HIP_TRY(hipMemsetAsync((int *)c->wz_cnt.p + 2 * sgpu::kWzMaxChunks, 0, sizeof(int), s));
+    // (the total of the chunks' exact pixels and the two deferral totals behind it)
+    if (c->wz_cnt.p) HIP_TRY(hipMemsetAsync((int *)c->wz_cnt.p + 2 * sgpu::kWzMaxChunks, 0, 3 * sizeof(int), s));
     // the WINSORIZED moment path's fallback list and record workspace
     // (stack_wz.h); SGPU_WZ=0 / 1 / 2 (default) / 3 / 4: off / one kernel /
     // two kernels (prep and rounds overlapped on two streams at N <= 128) /
@@ -516,9 +529,17 @@ int run_launch_body(sgpu_context *c, KParams k, bool has_shift) {
         // per-chunk tails (fallback sorted + exact kernels of a chunk on a third
         // stream, under the next chunks' work): counters zeroed per launch
         static const bool tails = !std::getenv("SGPU_WZ_TAILS") || std::atoi(std::getenv("SGPU_WZ_TAILS")) != 0;
-        if (tails && c->wz_cnt.ensure((2 * sgpu::kWzMaxChunks + 1) * sizeof(int)) == SGPU_OK) {
-            k.wz_tcnt = (int *)c->wz_cnt.p;
-            HIP_TRY(hipMemsetAsync(k.wz_tcnt, 0, (2 * sgpu::kWzMaxChunks + 1) * sizeof(int), s));
+        // split rounds (stack_wz.h): SGPU_WZ_SPLIT = rounds cap of the head pass
+        // (default 2; 0: the single nest); its stripe counters and the two
+        // deferral totals live behind the chunk counters (sgpu_kparams.h)
+        static const int split = std::getenv("SGPU_WZ_SPLIT") ? std::atoi(std::getenv("SGPU_WZ_SPLIT")) : 2;
+        if (c->wz_cnt.ensure(sgpu::kWzCntInts * sizeof(int)) == SGPU_OK) {
+            int *cb = (int *)c->wz_cnt.p;
+            HIP_TRY(hipMemsetAsync(cb, 0, (sgpu::kWzDefOff + 2) * sizeof(int), s));
+            if (tails) k.wz_tcnt = cb;
+            k.wz_split = split > 0 ? split : 0;
+            k.wz_scnt = cb + sgpu::kWzScntOff;
+            k.wz_def = cb + sgpu::kWzDefOff;
         }
         if (c->wz_ws.ensure(ws) == SGPU_OK) {
             k.wz_ws = c->wz_ws.p;

@@ -58,6 +58,9 @@ struct KParams {
     int *wz_tcnt;               // overlapped form: 2 counters per chunk (fb2, fb) + [kWzMaxChunks*2] the total
                                 // of the chunks' exact-kernel pixels, or null (tails after the last chunk)
     int wz_mode;                // 0 register-resident kernel only, 1 moment path in one kernel (LDS), 2 two kernels
+    int wz_split;               // LDS rounds, float, N <= 128: rounds cap of the head pass (SGPU_WZ_SPLIT; 0: one nest)
+    int *wz_scnt;               // split: stripe counters of the two deferral lists [2][kWzStripes * 16], or null
+    int *wz_def;                // split: [2] pixels that entered tail pass 1 / 2 (sgpu_last_wz_deferred), or null
     int wz_rw;                  // two-kernel form: rounds kernel -- 64 ranks staged in LDS (default, N <= 128), 4 / 5 / 6 global reads at that occupancy, 100 round-wise
     float *scratch;             // fallback kernel scratch
     long long scratch_threads;  // number of fallback threads the scratch covers
@@ -70,8 +73,34 @@ struct KParams {
     unsigned long long *prof;   // diagnostic builds (-DSGPU_PROF=1): per-section lane-cycles [16], or null
 };
 
+// Split rounds (stack_wz.h, k_stack_wz_rounds_lds / k_stack_wz_tail): the
+// pixels a pass hands on go to a striped list.  Stripe s takes the appends of
+// the head's blocks [s * bps, (s + 1) * bps) and owns entries [s * bps * 64,
+// (s + 1) * bps * 64) of the list -- room for every pixel of those blocks --
+// so a wave's append is one atomic on its stripe's counter (counters 64 B
+// apart), not on one word for the whole chunk.  A tail pass reads stripe s of
+// list_in and appends what it hands on again to stripe s of list_out.  An
+// entry names the pixel and the compact copy of its ranks (stack_wz.h,
+// wz_entry).
+struct WzSplit {
+    int cap;                    // rounds per pass (0: head only, no deferral)
+    int nstripes, bps;          // stripes in use, head blocks per stripe
+    const int *list_in, *cnt_in;
+    int *list_out, *cnt_out;
+    int *def;                   // tail: the pass's word of KParams::wz_def, or null
+};
+constexpr int kWzStripes = 1024;
+constexpr int kWzStripeStep = 16;   // ints between two stripe counters
+
 // most chunks of one launch whose tails run per chunk (KParams::wz_tcnt)
 constexpr int kWzMaxChunks = 256;
+// the context's counter block (ints): [0, 2 * kWzMaxChunks] KParams::wz_tcnt,
+// then the two words of KParams::wz_def (all zeroed per launch), and from
+// kWzScntOff the stripe counters KParams::wz_scnt (zeroed per chunk)
+constexpr int kWzDefOff = 2 * kWzMaxChunks + 1;
+constexpr int kWzScntOff = 1024;
+constexpr int kWzCntInts = kWzScntOff + 2 * kWzStripes * kWzStripeStep;
+static_assert(kWzDefOff + 2 <= kWzScntOff, "counter block layout");
 // rejection totals: one wave per pixel group ends with one pair of atomics;
 // on one address those serialise across the XCDs (hundreds of thousands of
 // waves per launch), so waves add into kCountStripes pairs 64 B apart and a

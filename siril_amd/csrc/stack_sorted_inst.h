@@ -13,6 +13,12 @@
 #define SGPU_WZ_RRW 4      // occupancy of the round-wise rounds kernel
 #endif
 
+#ifndef SGPU_WZ_TAIL_PASSES
+#define SGPU_WZ_TAIL_PASSES 2   // tail passes of the split rounds (1: one tail to the end; A/B)
+#endif
+static_assert(SGPU_WZ_TAIL_PASSES >= 1 && SGPU_WZ_TAIL_PASSES <= 2,
+              "each of the two stripe-counter sets is zeroed once per chunk and appended to by one pass");
+
 #include <algorithm>
 #include <cstdlib>
 
@@ -206,7 +212,7 @@ static int launch_one(const KParams &p, hipStream_t s) {
                 if constexpr (U16 && NP <= 128) {
                     if (p.wz_rw == 64)
                         hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP, 1>), dim3((unsigned)((q.wz_cnt + 63) / 64)), 64, 0,
-                                           s, q);
+                                           s, q, WzSplit{});   // 16-bit: the one nest
                     else
                         hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5, 1>), g2, 256, 0, s, q);
                 } else if constexpr (U16) {
@@ -228,10 +234,39 @@ static int launch_one(const KParams &p, hipStream_t s) {
                         case 4: hipLaunchKernelGGL((k_stack_wz_rounds<NP, 4>), g2, 256, 0, s, q); break;
                         case 6: hipLaunchKernelGGL((k_stack_wz_rounds<NP, 6>), g2, 256, 0, s, q); break;
                         case 64:   // LDS-staged ranks (default; R = 40 slots at NP <= 128: 10 KB per wave)
-                            if constexpr (NP <= 128)
-                                hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP>), dim3((unsigned)((q.wz_cnt + 63) / 64)),
-                                                   64, 0, s, q);
-                            else
+                            if constexpr (NP <= 128) {
+                                // split rounds (SGPU_WZ_SPLIT, default 2): the head runs
+                                // at most `cap` rounds per pixel and hands the rest, a few
+                                // lanes of nearly every wave, to compacted tail passes on
+                                // this stream -- before rounds[b] is recorded, so the
+                                // chunk's fallback tails (s3) see every append and the
+                                // next prep into buffer b finds records, state and lists
+                                // free.  Tail pass 1 defers again, the last one finishes.
+                                const unsigned nblk = (unsigned)((q.wz_cnt + 63) / 64);
+                                WzSplit sp{};
+                                if (p.wz_split > 0 && p.wz_scnt) {
+                                    sp.cap = p.wz_split;
+                                    sp.bps = (int)((nblk + kWzStripes - 1) / kWzStripes);
+                                    sp.nstripes = (int)((nblk + sp.bps - 1) / sp.bps);
+                                    sp.list_out = lists[0];
+                                    sp.cnt_out = p.wz_scnt;
+                                    if (hipMemsetAsync(p.wz_scnt, 0, 2 * kWzStripes * kWzStripeStep * sizeof(int), s) !=
+                                        hipSuccess)
+                                        return -1;
+                                }
+                                hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP>), dim3(nblk), 64, 0, s, q, sp);
+                                for (int pass = 0; sp.cap && pass < SGPU_WZ_TAIL_PASSES; pass++) {
+                                    sp.list_in = lists[pass & 1];
+                                    sp.cnt_in = p.wz_scnt + (pass & 1) * kWzStripes * kWzStripeStep;
+                                    sp.list_out = lists[(pass + 1) & 1];
+                                    sp.cnt_out = p.wz_scnt + ((pass + 1) & 1) * kWzStripes * kWzStripeStep;
+                                    sp.def = p.wz_def ? p.wz_def + pass : nullptr;
+                                    // 4 blocks per stripe: 4096 waves at 1024 stripes, the
+                                    // chip's 16 per CU
+                                    hipLaunchKernelGGL((k_stack_wz_tail<NP>), dim3((unsigned)sp.nstripes * 4u), 64, 0, s, q,
+                                                       sp, pass == SGPU_WZ_TAIL_PASSES - 1 ? 1 : 0);
+                                }
+                            } else
                                 hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5>), g2, 256, 0, s, q);
                             break;
                         default: hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5>), g2, 256, 0, s, q); break;

@@ -603,6 +603,53 @@ SG_HD int wz_finish(const RS &rs, int kept, double W1, double W2, float c0, int 
     return wz_final(rs, k, st, o);
 }
 
+// Split rounds (SGPU_WZ_SPLIT): at most `cap` rounds from the state st, then
+// the pixel is handed on with its state (route kWzDeferred; st holds what the
+// next pass resumes from, after wz_consts has rebuilt the constants).  cap <=
+// 0: no cap.  The rounds, their order and every value they compute are the
+// ones of wz_finish's loop, so a pixel resumed any number of times gets
+// wz_finish's result bit for bit (tests/hostsim/wz_split_main.cpp).
+constexpr int kWzDeferred = 5;
+template <int U16 = 0, class RS>
+SG_HD int wz_rounds_cap(const RS &rs, const WzConst &k, WzState &st, int cap, PixOut &o) {
+    bool more = true;
+    for (int r = 0; more; r++) {
+        if (r == cap) return kWzDeferred;
+        if (const int rc = wz_round<U16>(rs, k, st, more)) return rc;
+    }
+    return wz_final(rs, k, st, o);
+}
+
+// What the head leaves for the tail passes.  The ranks of a deferred pixel
+// are its column of the slot-major record: gathered from there, 64 listed
+// pixels touch nearly every line of the chunk's record (one pixel in 16 is
+// listed at sigma 3/3: the first build's tail pass re-read the whole record,
+// 0.67 GB per chunk, and halved the speed of the prep kernel running beside
+// it).  So the head copies the R ranks of its i-th deferring lane to words
+// [i * R, (i + 1) * R) of its own tile of the record -- the R x tw words of
+// its tw <= 64 pixels' columns, taken row after row -- which it has staged in
+// LDS and nobody reads again: a pixel's copy is R contiguous words in at most
+// two rows, and a tail lane reads three 64-byte sectors instead of R.
+// List entry: head block, index of the copy in the tile, lane (loc = 64 *
+// block + lane).
+SG_HD long long wz_crec_index(int f, int tw, long long cnt, long long col0) {
+    const int row = tw == 64 ? f >> 6 : f / tw, col = tw == 64 ? f & 63 : f % tw;
+    return (long long)row * cnt + col0 + col;
+}
+SG_HD int wz_entry(int block, int ci, int lane) { return (block << 12) | (ci << 6) | lane; }
+
+// wz_finish with a rounds cap: the head pass of the split
+template <int U16 = 0, class RS>
+SG_HD int wz_finish_cap(const RS &rs, int kept, double W1, double W2, float c0, int m, float slo_, float shi_,
+                        int cap, PixOut &o, WzState &st) {
+    WzConst k;
+    const int rc = wz_start<U16>(rs, kept, W1, W2, c0, m, slo_, shi_, k, st, o);
+    if (rc == 3) return 0;
+    if (rc == 4) return 2;
+    if (rc) return rc;
+    return wz_rounds_cap<U16>(rs, k, st, cap <= 0 ? -1 : cap, o);
+}
+
 // First half: sort the gathered column, store its ranks, and the window
 // moments about the first median c0 (one f64 pass; ranks >= kept hold +Inf
 // and add 0).  Returns 2 for the exact kernel (kept == 0), else 0.
@@ -1048,7 +1095,7 @@ void k_stack_wz_round(KParams p, int pass, int last) {
 // takes 10 KB: 16 waves per CU, the register-bound occupancy too.  (At the
 // round-3 R = 64 the LDS held 10 waves per CU and the staging lost.)
 template <int NP, int U16 = 0>
-__global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p) {
+__global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p, WzSplit sp) {
     using RS = RankStore<NP, 1>;
     __shared__ float s_rank[RS::R * 64];
     const int lane = (int)threadIdx.x;
@@ -1082,6 +1129,7 @@ __global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p) {
         const long long pix = p.wz_pix0 + loc;
         int route = 2;
         PixOut o;
+        WzState st;
         if (m.x > 0) {
             RS rs;
             rs.base = s_rank;
@@ -1094,10 +1142,46 @@ __global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p) {
             constexpr int G = NP / 64;
             const int N = p.nframes;
             const int el = (((N + G - 1) / G) + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1);
-            route = wz_finish<U16>(rs, m.x, p.wz_mom[loc], p.wz_mom[p.wz_cnt + loc],
-                                   (float)p.wz_mom[2 * p.wz_cnt + loc], G * el, p.sig0, p.sig1, o);
+            // (16-bit columns stay on the one nest: their kernel with the
+            // capped form measured 12.39 against 12.29 ms, winsorized100_u16)
+            if constexpr (U16)
+                route = wz_finish<U16>(rs, m.x, p.wz_mom[loc], p.wz_mom[p.wz_cnt + loc],
+                                       (float)p.wz_mom[2 * p.wz_cnt + loc], G * el, p.sig0, p.sig1, o);
+            else
+                route = wz_finish_cap<U16>(rs, m.x, p.wz_mom[loc], p.wz_mom[p.wz_cnt + loc],
+                                           (float)p.wz_mom[2 * p.wz_cnt + loc], G * el, p.sig0, p.sig1, sp.cap, o, st);
         }
-        if (route == 1) {
+        if (!U16 && route == kWzDeferred) {
+            // more rounds than the cap: the pixel goes to the tail pass with
+            // its state and a compact copy of its ranks (wz_crec_index); no
+            // result, no fallback list, no rejection totals
+            const unsigned long long dm = __ballot(true);          // the wave's deferring lanes
+            const int ci = (int)__popcll(dm & ((1ull << lane) - 1ull));
+            const long long col0 = (long long)blockIdx.x * 64;
+            const int tw = (int)(p.wz_cnt - col0 < 64 ? p.wz_cnt - col0 : 64);
+            const int stripe = (int)blockIdx.x / sp.bps;
+            const int slot = wave_append(sp.cnt_out + stripe * kWzStripeStep, true);
+            sp.list_out[stripe * sp.bps * 64 + slot] = wz_entry((int)blockIdx.x, ci, lane);
+            reinterpret_cast<WzState *>(p.wz_state)[loc] = st;
+            static_assert(RS::R % 4 == 0, "a copy is whole 16-byte pieces");
+            if (tw == 64 && (p.wz_cnt & 3) == 0) {
+                // full tile, rows 16-byte aligned: four words of the copy never
+                // straddle a row -- R / 4 wide stores, 32-bit index arithmetic
+                // (R * cnt words < 2^30: the launcher's bound)
+                const unsigned cnt = (unsigned)p.wz_cnt, c0w = (unsigned)col0;
+#pragma unroll 2
+                for (int j = 0; j < RS::R; j += 4) {
+                    const unsigned f = (unsigned)(ci * RS::R + j);
+                    const float4 q = make_float4(s_rank[j * 64 + lane], s_rank[(j + 1) * 64 + lane],
+                                                 s_rank[(j + 2) * 64 + lane], s_rank[(j + 3) * 64 + lane]);
+                    *reinterpret_cast<float4 *>(p.wz_ranks + (umul24(f >> 6, cnt) + c0w + (f & 63u))) = q;
+                }
+            } else {
+#pragma unroll 4
+                for (int j = 0; j < RS::R; j++)
+                    p.wz_ranks[wz_crec_index(ci * RS::R + j, tw, p.wz_cnt, col0)] = s_rank[j * 64 + lane];
+            }
+        } else if (route == 1) {
             const int slot = wave_append(p.fb2_count, true);
             p.fb2_list[slot] = (int)pix;
         } else if (route == 2) {
@@ -1110,6 +1194,111 @@ __global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p) {
             else write_result(p, pix, res, o.rl, o.rh);
             rl = o.rl;
             rh = o.rh;
+        }
+    }
+    add_counts(p, rl, rh);
+}
+
+// Tail pass of the split rounds: the pixels the pass before handed on, read
+// from its striped list (WzSplit).  One wave per block, as the head: the wave
+// stages the rank slots of 64 listed pixels in LDS (from the compact copies
+// the head left in its tiles, wz_crec_index), reloads their state, rebuilds
+// the constants (wz_consts) and runs
+// sp.cap more rounds -- every remaining round when `last`.  A pixel ends as in
+// the head: result, fallback lists, or sp.list_out again.  Block b takes
+// stripe b % nstripes and every (gridDim / nstripes)-th tile of it; the
+// stripe's count is read on the device (no host read-back).
+template <int NP>
+__global__ __launch_bounds__(64) void k_stack_wz_tail(KParams p, WzSplit sp, int last) {
+    using RS = RankStore<NP, 1>;
+    __shared__ float s_rank[RS::R * 64];
+    const int lane = (int)threadIdx.x;
+    const int stripe = (int)(blockIdx.x % (unsigned)sp.nstripes);
+    const int t0 = (int)(blockIdx.x / (unsigned)sp.nstripes), tstep = (int)(gridDim.x / (unsigned)sp.nstripes);
+    const int seg = stripe * sp.bps * 64;
+    int n = sp.cnt_in[stripe * kWzStripeStep];
+    n = n < sp.bps * 64 ? n : sp.bps * 64;           // never past the stripe's entries
+    if (t0 == 0 && lane == 0 && n > 0 && sp.def) atomicAdd(sp.def, n);
+    int rl = 0, rh = 0;
+    for (int i0 = t0 * 64; i0 < n; i0 += tstep * 64) {     // block-uniform trip count
+        const bool live = i0 + lane < n;
+        int ent = 0;
+        if (live) ent = sp.list_in[seg + i0 + lane];
+        const long long col0 = (long long)(ent >> 12) * 64;  // the head block's first pixel
+        const long long loc = col0 + (ent & 63);
+        int4 m = make_int4(0, 0, 0, 0);
+        if (live) m = reinterpret_cast<const int4 *>(p.wz_meta)[loc];
+        __syncthreads();                              // the tile before is through with s_rank
+        {
+            // the pixel's compact copy (wz_crec_index), every load issued
+            // before the first LDS store
+            float t[RS::R];
+            const int tw = (int)(p.wz_cnt - col0 < 64 ? p.wz_cnt - col0 : 64);
+            const int f0 = ((ent >> 6) & 63) * RS::R;
+            // full tile of a chunk whose rows are 16-byte aligned: the head's
+            // wide pieces; else (the chunk's partial last tile, an odd chunk) word by word
+            const bool wide = tw == 64 && (p.wz_cnt & 3) == 0;
+            const unsigned cnt = (unsigned)p.wz_cnt, c0w = (unsigned)col0;
+#pragma unroll
+            for (int j = 0; j < RS::R; j += 4) {
+                float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+                const unsigned f = (unsigned)(f0 + j);
+                if (live && wide)
+                    q = *reinterpret_cast<const float4 *>(p.wz_ranks + (umul24(f >> 6, cnt) + c0w + (f & 63u)));
+                t[j] = q.x;
+                t[j + 1] = q.y;
+                t[j + 2] = q.z;
+                t[j + 3] = q.w;
+            }
+            if (live && !wide) {
+#pragma unroll
+                for (int j = 0; j < RS::R; j++) t[j] = p.wz_ranks[wz_crec_index(f0 + j, tw, p.wz_cnt, col0)];
+            }
+#pragma unroll
+            for (int j = 0; j < RS::R; j++) s_rank[j * 64 + lane] = t[j];
+        }
+        __syncthreads();
+        if (live) {
+            const long long pix = p.wz_pix0 + loc;
+            int route = 2;
+            PixOut o;
+            WzState st;
+            if (m.x > 0) {
+                RS rs;
+                rs.base = s_rank;
+                rs.stride = 64;
+                rs.p = lane;
+                rs.kept = m.x;
+                rs.hi0 = m.y;
+                rs.mid0 = m.z;
+                rs.mid1 = m.w;
+                constexpr int G = NP / 64;
+                const int N = p.nframes;
+                const int el = (((N + G - 1) / G) + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1);
+                WzConst k;
+                float ymax, vmin;
+                route = wz_consts(rs, m.x, (float)p.wz_mom[2 * p.wz_cnt + loc], G * el, p.sig0, p.sig1, k, ymax, vmin);
+                st = reinterpret_cast<const WzState *>(p.wz_state)[loc];
+                o.fallback = 0;
+                if (!route) route = wz_rounds_cap(rs, k, st, last ? -1 : sp.cap, o);
+            }
+            if (route == kWzDeferred) {
+                const int slot = wave_append(sp.cnt_out + stripe * kWzStripeStep, true);
+                sp.list_out[seg + slot] = ent;       // its compact copy stays where it is
+                reinterpret_cast<WzState *>(p.wz_state)[loc] = st;
+            } else if (route == 1) {
+                const int slot = wave_append(p.fb2_count, true);
+                p.fb2_list[slot] = (int)pix;
+            } else if (route == 2) {
+                const int slot = wave_append(p.fb_count, true);
+                p.fb_list[slot] = (int)pix;
+            } else {
+                double res = o.res;
+                if (is_weighted(p)) res = weighted_mean(p, pix, (int)(pix % p.W), o.pmin, o.pmax, o.nkept);
+                write_result(p, pix, res, o.rl, o.rh);
+                rl += o.rl;
+                rh += o.rh;
+            }
         }
     }
     add_counts(p, rl, rh);

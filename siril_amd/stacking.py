@@ -206,6 +206,13 @@ class Context:
     def last_exact_pixels(self) -> int:
         return int(lib().sgpu_last_exact_pixels(self.h))
 
+    def last_wz_deferred(self):
+        """(pixels into tail pass 1, into tail pass 2) of the last float WINSORIZED
+        stack's split rounds (sgpu_last_wz_deferred); (0, 0) when the split did not run."""
+        a = (C.c_longlong * 2)()
+        check(lib().sgpu_last_wz_deferred(self.h, a), "sgpu_last_wz_deferred")
+        return int(a[0]), int(a[1])
+
     def set_seq_readers(self, readers: int):
         """Host threads per block read of a sequence stack (0: OMP_NUM_THREADS, else 8)."""
         check(lib().sgpu_set_seq_readers(self.h, int(readers)), "sgpu_set_seq_readers")
