@@ -46,8 +46,31 @@
 #ifndef SGPU_GW1024_LOOP
 #define SGPU_GW1024_LOOP 16, 3
 #endif
-// occupancy target of the moment path's prep kernel at NP = 128 (G = 2):
-// waves per SIMD the register allocation must allow
-#ifndef SGPU_WZ_PREP_W128
-#define SGPU_WZ_PREP_W128 4
+// The moment path's float prep kernel at NP = 128 has its own lanes per pixel
+// (the rounds kernels take it as a template argument; the fallback sorted
+// kernel keeps SGPU_GW128_LOOP's G): 4 (E = 32 slots per lane) or 2 (E = 64),
+// for unshifted frames and for shifted / normalized ones (XF) separately.
+// Its occupancy target -- waves per SIMD the register allocation must allow
+// -- per form: SGPU_WZ_PREP_W128 for four lanes, _G2 for two.
+#ifndef SGPU_WZ_PREP_G128
+#define SGPU_WZ_PREP_G128 4
 #endif
+#ifndef SGPU_WZ_PREP_G128_XF
+#define SGPU_WZ_PREP_G128_XF 4
+#endif
+#ifndef SGPU_WZ_PREP_W128
+#define SGPU_WZ_PREP_W128 6
+#endif
+#ifndef SGPU_WZ_PREP_W128_G2
+#define SGPU_WZ_PREP_W128_G2 4
+#endif
+// real-slot bounds of the four-lane prep (stack_sorted_rs128.hip): first
+// bound and step; rs_pick_prep4 takes the smallest one >= ceil(N / 4)
+#ifndef SGPU_WZ_PREP4_RS0
+#define SGPU_WZ_PREP4_RS0 20
+#endif
+#ifndef SGPU_WZ_PREP4_RSSTEP
+#define SGPU_WZ_PREP4_RSSTEP 4
+#endif
+static_assert((SGPU_WZ_PREP_G128 == 2 || SGPU_WZ_PREP_G128 == 4) &&
+              (SGPU_WZ_PREP_G128_XF == 2 || SGPU_WZ_PREP_G128_XF == 4), "prep kernel: 2 or 4 lanes per pixel");

@@ -8,6 +8,7 @@
 // rejection types want G = 1 (no cross-lane reductions at all).
 #pragma once
 #include "stack_sorted_impl.h"
+#include "stack_sorted_gw.h"
 #include "stack_wz.h"
 #ifndef SGPU_WZ_RRW
 #define SGPU_WZ_RRW 4      // occupancy of the round-wise rounds kernel
@@ -21,6 +22,7 @@ static_assert(SGPU_WZ_TAIL_PASSES >= 1 && SGPU_WZ_TAIL_PASSES <= 2,
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #ifndef SGPU_WZ_MOMENTS
 #define SGPU_WZ_MOMENTS 1        // 0: no moment-path kernels (WINSORIZED on the register-resident path only)
@@ -76,6 +78,10 @@ inline int wz_aux(WzAux *&a) {
 // NP has none (the full network runs)
 using KernelFn = void (*)(KParams);
 KernelFn rs_kernel_128(int kind, int xf, int rs);
+// the float prep kernel at NP = 128 with four lanes per pixel (E = 32) and
+// its own real-slot bounds (rs_pick_prep4; rs == 32: the full network)
+KernelFn prep4_kernel_128(int xf, int rs);
+int rs_pick_prep4(int N);
 KernelFn rs_kernel_256(int kind, int xf, int rs);
 KernelFn rs_kernel_512(int kind, int xf, int rs);
 template <int NP> inline KernelFn rs_kernel(int kind, int xf, int rs) {
@@ -126,7 +132,10 @@ static int launch_one(const KParams &p, hipStream_t s) {
     // (16-bit columns: the two-kernel form only; the single-kernel A/B forms
     // are float kernels)
     if constexpr (WZM) if (!U16 || (p.wz_mode >= 2 && p.wz_mode <= 4 && p.wz_ws)) {
-        if (p.fb2_list && p.wz_mode >= 2 && p.wz_mode <= 4 && p.wz_ws) {
+        // two-kernel form, PG lanes per pixel in the prep kernel: 0 done, 1 not
+        // on this path, 2 launched (the list-mode kernel follows), -1 error
+        auto two_kernel = [&](auto pg_tag) -> int {
+            constexpr int PG = decltype(pg_tag)::value;
             // two-kernel form: chunks of pixels whose records fit the workspace.
             // Overlapped: the workspace is split in two and the prep of chunk
             // k + 1 runs on a second stream while the rounds of chunk k run on
@@ -136,11 +145,13 @@ static int launch_one(const KParams &p, hipStream_t s) {
             // the chunks of 0.9 M pixels); 3: always overlapped; 4: never.
             const bool ovl = p.wz_mode == 3 || (p.wz_mode == 2 && NP <= 128);
             const int nbuf = ovl ? 2 : 1;
-            constexpr int R = RankStore<NP, G>::R;
+            constexpr int R = RankStore<NP, PG>::R;
+            constexpr int PE = NP / PG;
+            // occupancy target of the prep kernel (its own knob at NP = 128, float)
+            constexpr int PW = (NP == 128 && !U16) ? (PG == 4 ? SGPU_WZ_PREP_W128 : SGPU_WZ_PREP_W128_G2) : W;
             // per pixel: ranks, moments, meta, round-wise state and two lists
             const long long per = (long long)R * 4 + 3 * 8 + 16 + (long long)sizeof(WzState) + 8;
             const long long wsb = (p.wz_ws_bytes / nbuf) & ~4095LL;
-            static_assert(G == NP / 64 || NP < 128, "rounds kernels rebuild the prep kernel's G as NP / 64");
             long long ch = std::min<long long>(p.npix, ((wsb - 4096) / per) & ~255LL);
             // RankStore::fetch: umul24(slot, stride) -- stride < 2^24 and the
             // 32-bit product slot * stride < R * ch < 2^32
@@ -186,7 +197,15 @@ static int launch_one(const KParams &p, hipStream_t s) {
                 lists[1] = lists[0] + ch;
                 cnts = lists[1] + ch;                // 8 counters: pass k reads cnts[k], appends cnts[k + 1]
             };
-            const KernelFn prep_rs = (!U16 && rs < E) ? rs_kernel<NP>(0, p.shiftx ? 1 : 0, rs) : nullptr;
+            // the prep's real-slot variant, from the picker of its own G
+            KernelFn prep_rs = nullptr;
+            if constexpr (NP == 128 && !U16 && PG == 4) {
+                prep_rs = prep4_kernel_128(p.shiftx ? 1 : 0, rs_pick_prep4(p.nframes));
+                if (!prep_rs) return -1;
+            } else if constexpr (!U16 && PE == 64) {      // (the compiled variants: stack_sorted_rs*.hip)
+                const int prs = rs_pick(PE, PG, p.nframes);
+                if (prs < PE) prep_rs = rs_kernel<NP>(0, p.shiftx ? 1 : 0, prs);
+            }
             int k = 0;
             for (long long p0 = 0; p0 < p.npix; p0 += ch, k++) {
                 const int b = k % nbuf;
@@ -199,24 +218,26 @@ static int launch_one(const KParams &p, hipStream_t s) {
                     q.fb_list = p.fb_list + p0;
                     q.fb_count = p.wz_tcnt + 2 * k + 1;
                 }
-                const unsigned g1 = (unsigned)((q.wz_cnt * G + 255) / 256), g2 = (unsigned)((q.wz_cnt + 255) / 256);
+                const unsigned g1 = (unsigned)((q.wz_cnt * PG + 255) / 256), g2 = (unsigned)((q.wz_cnt + 255) / 256);
                 // the buffer's previous chunk must be through its rounds
                 if (ovl && k >= nbuf && hipStreamWaitEvent(sp, aux->rounds[b], 0) != hipSuccess) return -1;
                 if (prep_rs) {
                     if (!launch_fn(prep_rs, g1, 256, sp, q)) return -1;
-                } else if (p.shiftx) hipLaunchKernelGGL((k_stack_wz_prep<NP, G, 1, W, E, U16>), g1, 256, 0, sp, q);
-                else hipLaunchKernelGGL((k_stack_wz_prep<NP, G, 0, W, E, U16>), g1, 256, 0, sp, q);
+                } else if constexpr (NP == 128 && !U16 && PG == 4) {
+                    return -1;                       // (prep4_kernel_128 holds the full network too)
+                } else if (p.shiftx) hipLaunchKernelGGL((k_stack_wz_prep<NP, PG, 1, PW, PE, U16>), g1, 256, 0, sp, q);
+                else hipLaunchKernelGGL((k_stack_wz_prep<NP, PG, 0, PW, PE, U16>), g1, 256, 0, sp, q);
                 if (ovl && (hipEventRecord(aux->prep[b], sp) != hipSuccess ||
                             hipStreamWaitEvent(s, aux->prep[b], 0) != hipSuccess))
                     return -1;
                 if constexpr (U16 && NP <= 128) {
                     if (p.wz_rw == 64)
-                        hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP, 1>), dim3((unsigned)((q.wz_cnt + 63) / 64)), 64, 0,
+                        hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP, 1, PG>), dim3((unsigned)((q.wz_cnt + 63) / 64)), 64, 0,
                                            s, q, WzSplit{});   // 16-bit: the one nest
                     else
-                        hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5, 1>), g2, 256, 0, s, q);
+                        hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5, 1, PG>), g2, 256, 0, s, q);
                 } else if constexpr (U16) {
-                    hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5, 1>), g2, 256, 0, s, q);
+                    hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5, 1, PG>), g2, 256, 0, s, q);
                 } else if (p.wz_rw == 100) {
                     // round-wise: rounds 1..kPasses-1 one launch each, then the rest
                     constexpr int kPasses = 3;
@@ -226,13 +247,13 @@ static int launch_one(const KParams &p, hipStream_t s) {
                         q.wz_list_out = lists[(pass + 1) & 1];
                         q.wz_lcount = cnts + pass;
                         const unsigned gr = pass == 0 ? g2 : std::min<unsigned>(g2, 2048u);
-                        hipLaunchKernelGGL((k_stack_wz_round<NP, SGPU_WZ_RRW>), gr, 256, 0, s, q, pass,
+                        hipLaunchKernelGGL((k_stack_wz_round<NP, SGPU_WZ_RRW, PG>), gr, 256, 0, s, q, pass,
                                            pass == kPasses - 1 ? 1 : 0);
                     }
                 } else {
                     switch (p.wz_rw) {
-                        case 4: hipLaunchKernelGGL((k_stack_wz_rounds<NP, 4>), g2, 256, 0, s, q); break;
-                        case 6: hipLaunchKernelGGL((k_stack_wz_rounds<NP, 6>), g2, 256, 0, s, q); break;
+                        case 4: hipLaunchKernelGGL((k_stack_wz_rounds<NP, 4, 0, PG>), g2, 256, 0, s, q); break;
+                        case 6: hipLaunchKernelGGL((k_stack_wz_rounds<NP, 6, 0, PG>), g2, 256, 0, s, q); break;
                         case 64:   // LDS-staged ranks (default; R = 40 slots at NP <= 128: 10 KB per wave)
                             if constexpr (NP <= 128) {
                                 // split rounds (SGPU_WZ_SPLIT, default 2): the head runs
@@ -254,7 +275,7 @@ static int launch_one(const KParams &p, hipStream_t s) {
                                         hipSuccess)
                                         return -1;
                                 }
-                                hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP>), dim3(nblk), 64, 0, s, q, sp);
+                                hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP, 0, PG>), dim3(nblk), 64, 0, s, q, sp);
                                 for (int pass = 0; sp.cap && pass < SGPU_WZ_TAIL_PASSES; pass++) {
                                     sp.list_in = lists[pass & 1];
                                     sp.cnt_in = p.wz_scnt + (pass & 1) * kWzStripes * kWzStripeStep;
@@ -263,13 +284,13 @@ static int launch_one(const KParams &p, hipStream_t s) {
                                     sp.def = p.wz_def ? p.wz_def + pass : nullptr;
                                     // 4 blocks per stripe: 4096 waves at 1024 stripes, the
                                     // chip's 16 per CU
-                                    hipLaunchKernelGGL((k_stack_wz_tail<NP>), dim3((unsigned)sp.nstripes * 4u), 64, 0, s, q,
+                                    hipLaunchKernelGGL((k_stack_wz_tail<NP, PG>), dim3((unsigned)sp.nstripes * 4u), 64, 0, s, q,
                                                        sp, pass == SGPU_WZ_TAIL_PASSES - 1 ? 1 : 0);
                                 }
                             } else
-                                hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5>), g2, 256, 0, s, q);
+                                hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5, 0, PG>), g2, 256, 0, s, q);
                             break;
-                        default: hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5>), g2, 256, 0, s, q); break;
+                        default: hipLaunchKernelGGL((k_stack_wz_rounds<NP, 5, 0, PG>), g2, 256, 0, s, q); break;
                     }
                 }
                 if (hipGetLastError() != hipSuccess) return -1;
@@ -306,6 +327,23 @@ static int launch_one(const KParams &p, hipStream_t s) {
             }
             // every prep was joined into s by its rounds; the list-mode kernel
             // below runs on s after all of them
+            return 2;
+        };
+        if (p.fb2_list && p.wz_mode >= 2 && p.wz_mode <= 4 && p.wz_ws) {
+            // the prep's lanes per pixel: the sorted kernels' G, but at NP = 128,
+            // float, a constant of its own per shape (unshifted / shifted frames);
+            // a launch whose gather offsets do not fit 32 bits with it keeps G
+            constexpr int PG0 = (NP == 128 && !U16) ? SGPU_WZ_PREP_G128 : G;
+            constexpr int PG1 = (NP == 128 && !U16) ? SGPU_WZ_PREP_G128_XF : G;
+            auto fits = [&](int pg) {
+                return (unsigned long long)(pg - 1) * (unsigned long long)p.frame_stride * es +
+                           (unsigned long long)p.npix * es < 0xffffffffull;
+            };
+            int rc;
+            if (p.shiftx && fits(PG1)) rc = two_kernel(std::integral_constant<int, PG1>{});
+            else if (!p.shiftx && fits(PG0)) rc = two_kernel(std::integral_constant<int, PG0>{});
+            else rc = two_kernel(std::integral_constant<int, G>{});
+            if (rc != 2) return rc;
         } else if (p.fb2_list && p.wz_mode == 1) {
             constexpr int WW = NP <= 128 ? SGPU_WZ_W128 : SGPU_WZ_W;
             if (p.shiftx) hipLaunchKernelGGL((k_stack_wz<NP, G, 1, WW>), grid, 256, 0, s, p);

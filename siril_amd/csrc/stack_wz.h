@@ -309,6 +309,11 @@ SG_HD int wz_consts(const RS &rs, int kept, float c0, int m, float slo_, float s
                     float &vmin) {
     float vmax;
     if (!rs.fetch(0, vmin) || !rs.fetch(kept - 1, vmax)) return 1;
+    // m = G * el slots of the prep's G lanes.  Depth of its summation tree
+    // (wz_prepare): el / NACC chained adds per lane, NACC - 1 to combine the
+    // chains, log2 G lane combines (gsum_t) -- 14 + 1 + 2 = 17 at G = 4, N =
+    // 100 (el = 28); the depth passed, m / NACC + NACC + 9 = 67 there, bounds
+    // it for every G >= 1 (G * el / NACC >= el / NACC, 9 >= log2 G up to 512)
     k.sg = make_guard(vmin, vmax, m + 2, (m + SGPU_NACC - 1) / SGPU_NACC + SGPU_NACC + 9, kept);
     k.eps = (float)(4 * m + 64) * 0x1p-53f;
     k.sgc = (float)k.sg.c * 1.0001f;
@@ -951,7 +956,10 @@ void k_stack_wz_prep(KParams p) {
     }
 }
 
-template <int NP, int W, int U16 = 0>
+// PG (here and in the rounds kernels below): the lanes per pixel of the prep
+// kernel that wrote the records -- PG * el slots went into its moments, the
+// term count its error bounds take (the launcher passes the prep's own G)
+template <int NP, int W, int U16 = 0, int PG = NP / 64>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
 void k_stack_wz_rounds(KParams p) {
     using RS = RankStore<NP, 1>;
@@ -971,7 +979,7 @@ void k_stack_wz_rounds(KParams p) {
             rs.hi0 = m.y;
             rs.mid0 = m.z;
             rs.mid1 = m.w;
-            constexpr int G = NP / 64;         // the prep kernel's lanes per pixel (E = 64)
+            constexpr int G = PG;              // the prep kernel's lanes per pixel
             const int N = p.nframes;
             const int el = (((N + G - 1) / G) + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1);
             route = wz_finish<U16>(rs, m.x, p.wz_mom[loc], p.wz_mom[p.wz_cnt + loc],
@@ -1006,11 +1014,11 @@ void k_stack_wz_rounds(KParams p) {
 // against 0.44 for the nest.
 // (wave_append: stack_sorted_impl.h)
 
-template <int NP, int W>
+template <int NP, int W, int PG = NP / 64>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
 void k_stack_wz_round(KParams p, int pass, int last) {
     using RS = RankStore<NP, 1>;
-    constexpr int G = NP / 64;                 // the prep kernel's lanes per pixel (E = 64)
+    constexpr int G = PG;                      // the prep kernel's lanes per pixel
     const long long n = pass == 0 ? p.wz_cnt : (long long)p.wz_lcount[0];
     const long long stride = (long long)gridDim.x * blockDim.x;
     int rl = 0, rh = 0;
@@ -1094,7 +1102,7 @@ void k_stack_wz_round(KParams p, int pass, int last) {
 // (profiles/r05q_pmc_rounds.json).  At R = 40 slots (KT = 16, KM = 8) a wave
 // takes 10 KB: 16 waves per CU, the register-bound occupancy too.  (At the
 // round-3 R = 64 the LDS held 10 waves per CU and the staging lost.)
-template <int NP, int U16 = 0>
+template <int NP, int U16 = 0, int PG = NP / 64>
 __global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p, WzSplit sp) {
     using RS = RankStore<NP, 1>;
     __shared__ float s_rank[RS::R * 64];
@@ -1139,7 +1147,7 @@ __global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p, WzSplit s
             rs.hi0 = m.y;
             rs.mid0 = m.z;
             rs.mid1 = m.w;
-            constexpr int G = NP / 64;
+            constexpr int G = PG;
             const int N = p.nframes;
             const int el = (((N + G - 1) / G) + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1);
             // (16-bit columns stay on the one nest: their kernel with the
@@ -1208,7 +1216,7 @@ __global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p, WzSplit s
 // the head: result, fallback lists, or sp.list_out again.  Block b takes
 // stripe b % nstripes and every (gridDim / nstripes)-th tile of it; the
 // stripe's count is read on the device (no host read-back).
-template <int NP>
+template <int NP, int PG = NP / 64>
 __global__ __launch_bounds__(64) void k_stack_wz_tail(KParams p, WzSplit sp, int last) {
     using RS = RankStore<NP, 1>;
     __shared__ float s_rank[RS::R * 64];
@@ -1272,7 +1280,7 @@ __global__ __launch_bounds__(64) void k_stack_wz_tail(KParams p, WzSplit sp, int
                 rs.hi0 = m.y;
                 rs.mid0 = m.z;
                 rs.mid1 = m.w;
-                constexpr int G = NP / 64;
+                constexpr int G = PG;
                 const int N = p.nframes;
                 const int el = (((N + G - 1) / G) + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1);
                 WzConst k;
