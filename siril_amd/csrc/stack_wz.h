@@ -96,7 +96,7 @@ SG_HD int wz_clip_counts(const TS &ts, int lo, int hi, float mf, float tl0, floa
     float x;
     int k = 0;
     for (;;) {
-        if (lo + k >= hi || !ts.fetch(lo + k, x)) return 2;
+        if (lo + k >= hi || !ts.fetch_lo(lo + k, x)) return 2;
         if (!(mf - x > tl1)) break;
         k++;
     }
@@ -104,7 +104,7 @@ SG_HD int wz_clip_counts(const TS &ts, int lo, int hi, float mf, float tl0, floa
     cl = k;
     k = 0;
     for (;;) {
-        if (hi - 1 - k < lo + cl || !ts.fetch(hi - 1 - k, x)) return 2;
+        if (hi - 1 - k < lo + cl || !ts.fetch_hi(hi - 1 - k, x)) return 2;
         if (!(x - mf > th1)) break;
         k++;
     }
@@ -218,6 +218,26 @@ struct RankStore {
         x = (base + p)[umul24((unsigned)(ok ? slot : 0), (unsigned)stride)];
         return ok;
     }
+    // The same for a rank the caller reaches from one end of the window (r >=
+    // 0): only that end's region is tested and its slot formula used, one
+    // load issued (slot 0 on a miss); a rank outside the region -- past the
+    // stored depth, or in another region when they overlap (kept < R) --
+    // takes fetch() in a branch a wave rarely enters.  Same value, same
+    // answer as fetch() for every r.
+    SG_HD bool fetch_lo(int r, float &x) const {
+        const bool hit = r < KT && r < kept;
+        x = (base + p)[umul24((unsigned)(hit ? r : 0), (unsigned)stride)];
+        bool ok = true;
+        if (__builtin_expect(!hit, 0)) ok = fetch(r, x);
+        return ok;
+    }
+    SG_HD bool fetch_hi(int r, float &x) const {
+        const bool hit = r >= hi0 && r < kept;
+        x = (base + p)[umul24((unsigned)(hit ? r + (R - kept) : 0), (unsigned)stride)];
+        bool ok = true;
+        if (__builtin_expect(!hit, 0)) ok = fetch(r, x);
+        return ok;
+    }
 };
 
 // Bounds of the reference's (float)(vsum / (n - 1)) (siril_stats_float_sd,
@@ -328,40 +348,6 @@ SG_HD int wz_consts(const RS &rs, int kept, float c0, int m, float slo_, float s
     return 0;
 }
 
-#ifndef SGPU_WZ_BATCH
-#define SGPU_WZ_BATCH 0          // 1: four-rank batched walks (measured slower, 16.2-17.2 vs 15.8 ms: A/B only)
-#endif
-
-// Four consecutive ranks of one end of the window (r, r + d, r + 2d, r + 3d;
-// d = +1 from the low end, -1 from the high end), fetched as one batch of
-// independent loads and consumed in order: the walks of a round pay one load
-// latency per four samples instead of one per sample.  ok: bit j set when
-// rank j of the batch is stored (negative ranks are never fetched).
-struct RankRun {
-    float x0, x1, x2, x3;
-    unsigned ok;
-    int left;
-};
-template <class RS>
-SG_HD void run_fill(const RS &rs, RankRun &b, int r, int d) {
-    float *x[4] = {&b.x0, &b.x1, &b.x2, &b.x3};
-    b.ok = 0u;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int rj = r + j * d;
-        const bool ok = rs.fetch(rj < 0 ? 0 : rj, *x[j]) && rj >= 0;
-        b.ok |= ok ? (1u << j) : 0u;
-    }
-    b.left = 4;
-}
-SG_HD void run_pop(RankRun &b) {
-    b.x0 = b.x1;
-    b.x1 = b.x2;
-    b.x2 = b.x3;
-    b.ok >>= 1;
-    b.left--;
-}
-
 // take sample x out of the moments (one clamped or clipped sample)
 SG_HD void wz_take(float x, float c0, float eps, double &M1, double &M2, float &F1, float &F2) {
     const double y = (double)x - (double)c0;
@@ -369,6 +355,34 @@ SG_HD void wz_take(float x, float c0, float eps, double &M1, double &M2, float &
     M2 = fma(-y, y, M2);
     F1 += eps * fabsf((float)y);
     F2 += eps * (float)(y * y);
+}
+
+// One clamp walk of an iteration (rejection_float.c:229-237 on the sorted
+// window): the samples below Lhi at the low end (HI = 0: ranks r0 + cnt
+// upwards) or above Ulo at the high end (HI = 1: ranks r0 - cnt downwards)
+// leave the moments, lows ascending, highs descending.  nx is the next
+// sample, already fetched; cnt the samples this end has given up, other those
+// of the other end.  A trip is one straight line: take nx, fetch the next
+// rank from this end's region of the record (fetch_lo / fetch_hi), and note
+// in `bad` (sticky) what ends the pixel's moment path -- no sample left
+// between the ends (cnt + other >= n), or the next rank not stored.  A bad
+// lane leaves the walk at once, takes nothing more in this or the other walk,
+// and the caller returns 1 after the iteration's arithmetic.  The fetch is
+// issued whatever the count says (no branch around it), so at the high end
+// the rank is kept from falling below 0; what it reads then is never used.
+// (Trips of K = 2, 3 and 4 samples -- K rows of the record at constant
+// offsets from one address, sample j taken when the ones before it were --
+// measured slower the larger K: DESIGN.md section 8.)
+template <int HI, class RS>
+SG_HD void wz_walk(const RS &rs, int r0, float bound, float c0, float eps, int n, int other, int &cnt, float &nx,
+                   double &M1, double &M2, float &F1, float &F2, bool &bad) {
+    while ((HI ? nx > bound : nx < bound) && !bad) {
+        wz_take(nx, c0, eps, M1, M2, F1, F2);
+        cnt++;
+        const int r = HI ? (r0 - cnt > 0 ? r0 - cnt : 0) : r0 + cnt;
+        const bool ok = HI ? rs.fetch_hi(r, nx) : rs.fetch_lo(r, nx);
+        bad = cnt + other >= n || !ok;
+    }
 }
 
 // One rejection round of the pixel on moments (rejection_float.c:223-259,
@@ -381,43 +395,29 @@ SG_HD int wz_round(const RS &rs, const WzConst &k, WzState &st, bool &more) {
     int lo = st.lo, hi = st.hi;
     const int n = hi - lo;
     const double rn = 1.0 / n, rn1 = 1.0 / (n - 1);
-#if SGPU_WZ_BATCH
-    // one batch of independent loads: the median pair and four ranks at each
-    // end of the window (the window ends, the first samples the clamps and
-    // the clip walk reach)
-    float ma, mb;
-    const bool okm = rs.fetch(lo + n / 2 - ((n & 1) ? 0 : 1), ma) & rs.fetch(lo + n / 2, mb);
-    RankRun e0, e1;                        // ranks lo.. and hi-1.. as of the round start
-    run_fill(rs, e0, lo, 1);
-    run_fill(rs, e1, hi - 1, -1);
-    if (!okm || !(e0.ok & e1.ok & 1u)) return 1;
-    const float mf = median_from(ma, mb, n);
-    SGPU_WZ_TRACE(0);
-    const float xw0 = e0.x0, xw1 = e1.x0;
-#else
     float ma, mb;
     if (!rs.fetch(lo + n / 2 - ((n & 1) ? 0 : 1), ma) || !rs.fetch(lo + n / 2, mb)) return 1;
     const float mf = median_from(ma, mb, n);
     SGPU_WZ_TRACE(0);
     float xw0, xw1;
-    if (!rs.fetch(lo, xw0) || !rs.fetch(hi - 1, xw1)) return 1;
-#endif
+    if (!rs.fetch_lo(lo, xw0) || !rs.fetch_hi(hi - 1, xw1)) return 1;
     // the round's first sd (siril_stats_float_sd of the window, :226)
     float vlo, vhi;
     const bool flat = xw0 == xw1;         // constant window: every sd below is exactly 0
     var_bounds(st.W1, st.W2, st.E1, st.E2, 0, 0, n, c0, 0.f, 0.f, 0.f, 0.f, false, eps, sgc, rn, rn1, vlo, vhi);
     if (flat) vlo = vhi = 0.f;
     float slo = sqrt_lo(vlo), shi = sqrt_hi(vhi);
-    // clamp iterations (:229-237)
+    // clamp iterations (:229-237).  The loop has one exit: what would end the
+    // pixel's moment path (a walk's `bad`, a sigma bound that is not finite,
+    // the iteration cap, a stop test the interval does not decide) is
+    // collected in `bad` and returned after it, so the state below is
+    // updated in place and nothing is copied on the way round.
     float Llo = -f_inf(), Lhi = -f_inf(), Ulo = f_inf(), Uhi = f_inf();
     int a = 0, c = 0;
     double R1 = st.W1, R2 = st.W2;
     float F1 = st.E1, F2 = st.E2;
-#if SGPU_WZ_BATCH
-    RankRun wl = e0, wh = e1;             // next samples to clamp: wl.x0 = rank lo + a, wh.x0 = rank hi - 1 - c
-#else
     float nlo = xw0, nhi = xw1;           // next samples to clamp: ranks lo + a, hi - 1 - c
-#endif
+    bool bad = false;
     for (int it = 0;;) {
         const float tlo = 1.5f * slo, thi = 1.5f * shi;
         float m0lo = mf - thi, m0hi = mf - tlo, m1lo = mf + tlo, m1hi = mf + thi;
@@ -431,89 +431,26 @@ SG_HD int wz_round(const RS &rs, const WzConst &k, WzState &st, bool &more) {
         Lhi = fminf(m1hi, fmaxf(m0hi, Lhi));
         Ulo = fminf(m1lo, fmaxf(m0lo, Ulo));
         Uhi = fminf(m1hi, fmaxf(m0hi, Uhi));
-#if SGPU_WZ_BATCH
-        while (wl.x0 < Lhi) {
-            wz_take(wl.x0, c0, eps, R1, R2, F1, F2);
-            if (++a + c >= n) return 1;
-            run_pop(wl);
-            if (wl.left == 0) run_fill(rs, wl, lo + a, 1);
-            if (!(wl.ok & 1u)) return 1;
-        }
-        while (wh.x0 > Ulo) {
-            wz_take(wh.x0, c0, eps, R1, R2, F1, F2);
-            if (a + ++c >= n) return 1;
-            run_pop(wh);
-            if (wh.left == 0) run_fill(rs, wh, hi - 1 - c, -1);
-            if (!(wh.ok & 1u)) return 1;
-        }
-#else
-        while (nlo < Lhi) {
-            wz_take(nlo, c0, eps, R1, R2, F1, F2);
-            if (++a + c >= n || !rs.fetch(lo + a, nlo)) return 1;
-        }
-        while (nhi > Ulo) {
-            wz_take(nhi, c0, eps, R1, R2, F1, F2);
-            if (a + ++c >= n || !rs.fetch(hi - 1 - c, nhi)) return 1;
-        }
-#endif
+        wz_walk<0>(rs, lo, Lhi, c0, eps, n, c, a, nlo, R1, R2, F1, F2, bad);
+        wz_walk<1>(rs, hi - 1, Ulo, c0, eps, n, a, c, nhi, R1, R2, F1, F2, bad);
         SGPU_WZ_TRACE(1);
         var_bounds(R1, R2, F1, F2, a, c, n, c0, Llo, Lhi, Ulo, Uhi, true, eps, sgc, rn, rn1, vlo, vhi);
         if (flat) vlo = vhi = 0.f;
-        if (!(vhi - vhi == 0.f)) return 1;
+        bad |= !(vhi - vhi == 0.f);
         const float s0lo = slo, s0hi = shi;
         slo = 1.134f * sqrt_lo(vlo);
         shi = 1.134f * sqrt_hi(vhi);
         const float A = slo - s0hi, B = shi - s0lo;      // fl(sigma - sigma0) in [A, B]
         const float dmin = A > 0.f ? A : (B < 0.f ? -B : 0.f);
         const float dmax = fmaxf(fabsf(A), fabsf(B));
-        if (dmin > s0hi * 0.0005f) {
-            if (++it > kWinsorCap) return 1;
-            continue;
-        }
-        if (dmax <= s0lo * 0.0005f) break;
-        return 1;
+        const bool go = dmin > s0hi * 0.0005f;           // another iteration; else it must be a sure stop
+        it += go ? 1 : 0;
+        bad |= go ? it > kWinsorCap : !(dmax <= s0lo * 0.0005f);
+        if (!go || bad) break;
     }
+    if (bad) return 1;
     // sigma_clipping_float (:238-246) with sigma in [slo, shi]
     int cl = 0, ch = 0;
-#if SGPU_WZ_BATCH
-    // the clip candidates are the window's first ranks from each end: walked
-    // from the round-start batches (more only past four candidates), and
-    // taken out of the moments as they are counted -- the same samples, in
-    // the same order (lows ascending, then highs descending), that the
-    // round-3 form subtracted after cutoff_round; a pixel that leaves below
-    // (ambiguous, order-dependent cutoff) discards st
-    if (n - st.r > 4) {
-        const float tl0 = slo * k.slo_, th0 = slo * k.shi_, tl1 = shi * k.slo_, th1 = shi * k.shi_;
-        if (!(tl0 >= 0.f && th0 >= 0.f)) return 2;
-        float x;
-        RankRun b = e0;
-        for (int j = 0;; j++) {
-            if (lo + j >= hi) return 1;
-            if (b.left == 0) run_fill(rs, b, lo + j, 1);
-            if (!(b.ok & 1u)) return 1;
-            x = b.x0;
-            if (!(mf - x > tl1)) break;
-            wz_take(x, c0, eps, st.W1, st.W2, st.E1, st.E2);
-            run_pop(b);
-            cl++;
-        }
-        if (mf - x > tl0) return 1;
-        b = e1;
-        for (int j = 0;; j++) {
-            if (hi - 1 - j < lo + cl) return 1;
-            if (b.left == 0) run_fill(rs, b, hi - 1 - j, -1);
-            if (!(b.ok & 1u)) return 1;
-            x = b.x0;
-            if (!(x - mf > th1)) break;
-            wz_take(x, c0, eps, st.W1, st.W2, st.E1, st.E2);
-            run_pop(b);
-            ch++;
-        }
-        if (x - mf > th0) return 1;
-    }
-    bool changed;
-    if (cutoff_round(n, st.r, cl, ch, lo, hi, st.rl, st.rh, changed)) return 2;
-#else
     if (n - st.r > 4) {
         const float tl0 = slo * k.slo_, th0 = slo * k.shi_, tl1 = shi * k.slo_, th1 = shi * k.shi_;
         if (!(tl0 >= 0.f && th0 >= 0.f)) return 2;
@@ -523,13 +460,16 @@ SG_HD int wz_round(const RS &rs, const WzConst &k, WzState &st, bool &more) {
     const int lo0 = lo, hi0 = hi;
     bool changed;
     if (cutoff_round(n, st.r, cl, ch, lo, hi, st.rl, st.rh, changed)) return 2;
-    for (int j = 0; j < lo - lo0 + (hi0 - hi); j++) {
+    for (int j = 0; j < lo - lo0; j++) {
         float x;
-        const int rk = j < lo - lo0 ? lo0 + j : hi0 - 1 - (j - (lo - lo0));
-        if (!rs.fetch(rk, x)) return 1;
+        if (!rs.fetch_lo(lo0 + j, x)) return 1;
         wz_take(x, c0, eps, st.W1, st.W2, st.E1, st.E2);
     }
-#endif
+    for (int j = 0; j < hi0 - hi; j++) {
+        float x;
+        if (!rs.fetch_hi(hi0 - 1 - j, x)) return 1;
+        wz_take(x, c0, eps, st.W1, st.W2, st.E1, st.E2);
+    }
     st.lo = lo;
     st.hi = hi;
     more = changed && hi - lo > 3;
@@ -806,6 +746,9 @@ struct ColStore {
         x = base[ok ? r : 0];
         return ok;
     }
+    // every rank is stored: RankStore's end fetches are plain reads here
+    SG_HD bool fetch_lo(int r, float &x) const { return fetch(r, x); }
+    SG_HD bool fetch_hi(int r, float &x) const { return fetch(r, x); }
 };
 
 // From the sorted column (ranks 0..N-1 in row[], missing samples +Inf at
