@@ -81,6 +81,19 @@ __device__ double quickmedian(float *a, int n) {
     return (n % 2 == 0) ? ((double)a[k - 1] + a[k]) / 2.0 : (double)a[k];
 }
 
+// quickmedian where only its value is used (kept == 0, median_and_mean.c:1040;
+// the median stack): a column of one repeated sample -- every frame null, the
+// border that registration shifts leave uncovered -- answers with that sample.
+// The partition above (strict <) moves `left` one element per pass on such a
+// column, n^2 / 2 steps: 137 s for one pixel of a 65536-frame stack.
+__device__ double quickmedian_value(float *a, int n) {
+    const uint32_t b0 = __float_as_uint(a[0]);             // (bit patterns: -0 is not +0 in the result)
+    int i = 1;
+    while (i < n && __float_as_uint(a[i]) == b0) i++;
+    if (i == n && n >= 9) return (n % 2 == 0) ? ((double)a[0] + a[0]) / 2.0 : (double)a[0];
+    return quickmedian(a, n);
+}
+
 __device__ void insertion_sort(float *a, int n) {
     for (int i = 1; i < n; i++) {
         const float v = a[i];
@@ -364,7 +377,7 @@ __device__ int apply_rejection(const KParams &p, Work &wk, int nb, int crej[2], 
 // mean_and_reject, float branch (median_and_mean.c:1038-1099)
 __device__ double mean_and_reject(const KParams &p, Work &wk, int n, int rej[2], long long pix, int x) {
     const int kept = apply_rejection(p, wk, n, rej, pix, x);
-    if (kept == 0) return quickmedian(wk.stack, n);
+    if (kept == 0) return quickmedian_value(wk.stack, n);
     if (is_weighted(p)) {
         float pmin = FLT_MAX, pmax = -FLT_MAX;
         for (int f = 0; f < kept; ++f) {
@@ -427,7 +440,7 @@ __device__ __forceinline__ void exact_body(const KParams &p, int all_pixels, flo
         }
         int rej[2] = {0, 0};
         double res;
-        if (p.rtype == KMEDIAN) res = ex::quickmedian(wk.stack, N);
+        if (p.rtype == KMEDIAN) res = ex::quickmedian_value(wk.stack, N);
         else res = ex::mean_and_reject(p, wk, N, rej, pix, x);
         write_result(p, pix, res, rej[0], rej[1]);
         c0 += rej[0];
@@ -747,6 +760,15 @@ __device__ double quickmedian(WORD *a, int n) {         // sorting.c:195-230
     return (n % 2 == 0) ? ((double)a[k - 1] + (double)a[k]) / 2.0 : (double)a[k];
 }
 
+// as ex::quickmedian_value: a column of one repeated WORD (null, or saturated)
+__device__ double quickmedian_value(WORD *a, int n) {
+    const WORD a0 = a[0];
+    int i = 1;
+    while (i < n && a[i] == a0) i++;
+    if (i == n && n >= 9) return (double)a0;               // ((double)a0 + (double)a0) / 2.0 is a0
+    return quickmedian(a, n);
+}
+
 __device__ void sort(WORD *a, int n) {                   // quicksort_s: result is the sorted array
     for (int i = 1; i < n; i++) {                        // (insertion sort; equal keys are identical)
         const WORD v = a[i];
@@ -1000,7 +1022,7 @@ __device__ int apply_rejection(const KParams &p, Work &wk, int nb, int crej[2], 
 
 __device__ double mean_and_reject(const KParams &p, Work &wk, int n, int rej[2], long long pix, int x) {
     const int kept = apply_rejection(p, wk, n, rej, pix, x);
-    if (kept == 0) return quickmedian(wk.stack, n);
+    if (kept == 0) return quickmedian_value(wk.stack, n);
     if (is_weighted(p)) {
         WORD pmin = 65535, pmax = 0;
         for (int f = 0; f < kept; ++f) {
@@ -1084,7 +1106,7 @@ __device__ __forceinline__ void exact16_body(const KParams &p, int all_pixels, f
         }
         int rej[2] = {0, 0};
         double res;
-        if (p.rtype == KMEDIAN) res = ex16::quickmedian(wk.stack, N);
+        if (p.rtype == KMEDIAN) res = ex16::quickmedian_value(wk.stack, N);
         else res = ex16::mean_and_reject(p, wk, N, rej, pix, x);
         if (p.out_f32) {
             float fr = (float)res * .000015259022f;          // double_ushort_to_float_range
