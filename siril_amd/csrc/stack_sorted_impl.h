@@ -1714,7 +1714,12 @@ __device__ __forceinline__ void add_counts(const KParams &p, int rl, int rh) {
 #ifndef SGPU_GATHER_SLOTSTEP
 #define SGPU_GATHER_SLOTSTEP 1
 #endif
-template <int XF, int E, int G, bool DROP_ZERO, int U16 = 0, int RS = E, bool SLOTSTEP = SGPU_GATHER_SLOTSTEP>
+// NFLOOR: the launch's N is in the real-slot bucket of RS (rs_pick: N > G * (RS
+// - step)), so the slots every N of the bucket fills lie before the runtime
+// stop: no `past the stop` select for them (their uniform compares, one SGPR
+// pair each, were the one-lane prep's spilled SGPRs).
+template <int XF, int E, int G, bool DROP_ZERO, int U16 = 0, int RS = E, bool SLOTSTEP = SGPU_GATHER_SLOTSTEP,
+          bool NFLOOR = false>
 __device__ __forceinline__ void gather_column(const KParams &p, float (&v)[E], long long pix, int x,
                                               int g, int &kept, int &bad) {
     const int N = p.nframes;
@@ -1809,7 +1814,8 @@ __device__ __forceinline__ void gather_column(const KParams &p, float (&v)[E], l
     for (int e = RS; e < E; e++) v[e] = f_inf();
 #pragma unroll
     for (int e = 0; e < RS; e++) {
-        float val = (!GSTOP || e < elg) ? raw[e] : 0.f;   // past the stop: a missing sample
+        constexpr int EMIN = NFLOOR ? RS - (E == 64 ? 4 : 8) : 0;   // slots before the stop for every N of the bucket
+        float val = (!GSTOP || e < EMIN || e < elg) ? raw[e] : 0.f;   // past the stop: a missing sample
         if (XF) {
             const int fe = min(e * G + g, N - 1);
             const int sh = p.shiftx[fe];

@@ -82,6 +82,10 @@ KernelFn rs_kernel_128(int kind, int xf, int rs);
 // its own real-slot bounds (rs_pick_prep4; rs == 32: the full network)
 KernelFn prep4_kernel_128(int xf, int rs);
 int rs_pick_prep4(int N);
+// the same with one lane per pixel (k_stack_wz_prep1; E = 128): bounds 72 ..
+// 120 in steps of 8 and the full network (rs == 128)
+KernelFn prep1_kernel_128(int xf, int rs);
+int rs_pick_prep1(int N);
 KernelFn rs_kernel_256(int kind, int xf, int rs);
 KernelFn rs_kernel_512(int kind, int xf, int rs);
 template <int NP> inline KernelFn rs_kernel(int kind, int xf, int rs) {
@@ -148,7 +152,10 @@ static int launch_one(const KParams &p, hipStream_t s) {
             constexpr int R = RankStore<NP, PG>::R;
             constexpr int PE = NP / PG;
             // occupancy target of the prep kernel (its own knob at NP = 128, float)
-            constexpr int PW = (NP == 128 && !U16) ? (PG == 4 ? SGPU_WZ_PREP_W128 : SGPU_WZ_PREP_W128_G2) : W;
+            constexpr int PW = (NP == 128 && !U16) ? (PG == 4 ? SGPU_WZ_PREP_W128 : PG == 2 ? SGPU_WZ_PREP_W128_G2
+                                                                                            : SGPU_WZ_PREP_W128_G1)
+                                                   : W;
+            (void)PW;
             // per pixel: ranks, moments, meta, round-wise state and two lists
             const long long per = (long long)R * 4 + 3 * 8 + 16 + (long long)sizeof(WzState) + 8;
             const long long wsb = (p.wz_ws_bytes / nbuf) & ~4095LL;
@@ -199,8 +206,12 @@ static int launch_one(const KParams &p, hipStream_t s) {
             };
             // the prep's real-slot variant, from the picker of its own G
             KernelFn prep_rs = nullptr;
+            constexpr bool kOwnPrep = NP == 128 && !U16 && (PG == 4 || PG == 1);   // every bound in its picker
             if constexpr (NP == 128 && !U16 && PG == 4) {
                 prep_rs = prep4_kernel_128(p.shiftx ? 1 : 0, rs_pick_prep4(p.nframes));
+                if (!prep_rs) return -1;
+            } else if constexpr (NP == 128 && !U16 && PG == 1) {
+                prep_rs = prep1_kernel_128(p.shiftx ? 1 : 0, rs_pick_prep1(p.nframes));
                 if (!prep_rs) return -1;
             } else if constexpr (!U16 && PE == 64) {      // (the compiled variants: stack_sorted_rs*.hip)
                 const int prs = rs_pick(PE, PG, p.nframes);
@@ -223,8 +234,8 @@ static int launch_one(const KParams &p, hipStream_t s) {
                 if (ovl && k >= nbuf && hipStreamWaitEvent(sp, aux->rounds[b], 0) != hipSuccess) return -1;
                 if (prep_rs) {
                     if (!launch_fn(prep_rs, g1, 256, sp, q)) return -1;
-                } else if constexpr (NP == 128 && !U16 && PG == 4) {
-                    return -1;                       // (prep4_kernel_128 holds the full network too)
+                } else if constexpr (kOwnPrep) {
+                    return -1;                       // (prep4_kernel_128 / prep1_kernel_128 hold the full network too)
                 } else if (p.shiftx) hipLaunchKernelGGL((k_stack_wz_prep<NP, PG, 1, PW, PE, U16>), g1, 256, 0, sp, q);
                 else hipLaunchKernelGGL((k_stack_wz_prep<NP, PG, 0, PW, PE, U16>), g1, 256, 0, sp, q);
                 if (ovl && (hipEventRecord(aux->prep[b], sp) != hipSuccess ||
@@ -335,7 +346,10 @@ static int launch_one(const KParams &p, hipStream_t s) {
             // a launch whose gather offsets do not fit 32 bits with it keeps G
             constexpr int PG0 = (NP == 128 && !U16) ? SGPU_WZ_PREP_G128 : G;
             constexpr int PG1 = (NP == 128 && !U16) ? SGPU_WZ_PREP_G128_XF : G;
+            // (one lane: trivially true; its kernels are compiled for the N of
+            // this capacity's real-slot buckets, 65 .. 128)
             auto fits = [&](int pg) {
+                if (pg == 1) return p.nframes > NP / 2;
                 return (unsigned long long)(pg - 1) * (unsigned long long)p.frame_stride * es +
                            (unsigned long long)p.npix * es < 0xffffffffull;
             };

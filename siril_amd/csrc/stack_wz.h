@@ -201,6 +201,40 @@ struct RankStore {
             if (e >= em0 && e <= em1) __builtin_amdgcn_raw_buffer_store_b32(x, rmid, (int)(bmid + eo), 0, 0);
         }
     }
+    // store_buf for a sorted column in one lane (G = 1, slot = rank) whose
+    // wave has kept in [RSL - 7, RSL] in every lane: the slots that can hold
+    // a rank of the high region, [RSL - 7 - KT, RSL), and of the middle one,
+    // [(RSL - 7) / 2 - KM / 2, RSL / 2 + KM / 2), are compile-time supersets
+    // of every lane's ranges, so the stores stand in a straight line; a slot
+    // outside the lane's own range falls outside the region (offsets -7 .. 22
+    // and -4 .. 11 slots: no wrap back into it) and is dropped as in
+    // store_buf.  Every rank of the three ranges is stored, so hi0 / mid0 /
+    // mid1 are the unclipped ones -- what store() leaves for this wave.
+    template <int RSL>
+    __device__ void store_full(const float (&v)[E]) {
+        static_assert(G == 1 && RSL % 8 == 0 && RSL - 7 - KT >= KT && RSL <= E, "one lane per pixel, N >= 65");
+        mid0 = kept / 2 - KM / 2;
+        mid1 = mid0 + KM;
+        hi0 = kept - KT;
+        const uint32_t S4 = (uint32_t)stride * 4u;
+        const uint32_t pb = (uint32_t)p * 4u;
+        const auto rlo = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)((uint32_t)KT * S4), 0x00020000);
+        const auto rmid = __builtin_amdgcn_make_buffer_rsrc(base + (long long)KT * stride, (short)0,
+                                                            (int)((uint32_t)KM * S4), 0x00020000);
+        const auto rhi = __builtin_amdgcn_make_buffer_rsrc(base + (long long)(KT + KM) * stride, (short)0,
+                                                           (int)((uint32_t)KT * S4), 0x00020000);
+        const uint32_t bhi = pb + (uint32_t)(KT - kept) * S4;
+        const uint32_t bmid = pb - (uint32_t)mid0 * S4;
+#pragma unroll
+        for (int e = 0; e < KT; e++)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[e]), rlo, (int)(pb + (uint32_t)e * S4), 0, 0);
+#pragma unroll
+        for (int e = RSL / 2 - 4 - KM / 2; e < RSL / 2 + KM / 2; e++)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[e]), rmid, (int)(bmid + (uint32_t)e * S4), 0, 0);
+#pragma unroll
+        for (int e = RSL - 7 - KT; e < RSL; e++)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[e]), rhi, (int)(bhi + (uint32_t)e * S4), 0, 0);
+    }
 #endif
     // rank r (0 <= r < kept); false when not stored (the pixel falls back).
     // Branch-free: the slot is selected, one load is issued (slot 0 when the
@@ -333,7 +367,10 @@ SG_HD int wz_consts(const RS &rs, int kept, float c0, int m, float slo_, float s
     // (wz_prepare): el / NACC chained adds per lane, NACC - 1 to combine the
     // chains, log2 G lane combines (gsum_t) -- 14 + 1 + 2 = 17 at G = 4, N =
     // 100 (el = 28); the depth passed, m / NACC + NACC + 9 = 67 there, bounds
-    // it for every G >= 1 (G * el / NACC >= el / NACC, 9 >= log2 G up to 512)
+    // it for every G >= 1 (G * el / NACC >= el / NACC, 9 >= log2 G up to 512).
+    // One lane per pixel (wz_prepare1, G = 1): m = el (100 at N = 100, where
+    // four lanes gave 112), el / NACC chained adds + NACC - 1 combines and no
+    // lane level -- 50 + 1 against the 100 / 2 + 2 + 9 = 61 passed
     k.sg = make_guard(vmin, vmax, m + 2, (m + SGPU_NACC - 1) / SGPU_NACC + SGPU_NACC + 9, kept);
     k.eps = (float)(4 * m + 64) * 0x1p-53f;
     k.sgc = (float)k.sg.c * 1.0001f;
@@ -897,6 +934,132 @@ void k_stack_wz_prep(KParams p) {
         m.w = rs.mid1;
         reinterpret_cast<int4 *>(p.wz_meta)[loc] = m;
     }
+}
+
+// One lane per pixel (NP = 128, float): the column sorted in one lane has no
+// cross-lane merge (v_med3 + lane exchanges) and no interleave; what the
+// four-lane form spends there is 60 instructions a pixel against the 36 of
+// oem_sort<128, 104>.  The kernel is written for the wave that has (nearly)
+// every sample -- every lane's kept >= RSL - 7, the lowest N of the real-slot
+// bucket (rs_pick: N in [RSL - 7, RSL]) -- because then everything that
+// depends on `kept` lies in compile-time slot ranges:
+//   * ranks [kept - KT, kept) in slots [RSL - 7 - KT, RSL), ranks
+//     [kept / 2 - KM / 2, kept / 2 + KM / 2) in [RSL / 2 - KM, RSL / 2 + KM /
+//     2): with the low KT slots 51 unconditional stores through the region
+//     descriptors of store_buf (RankStore::store_full), no branch;
+//   * the two ranks of the first median in slots [RSL / 2 - 4, RSL / 2];
+//   * +Inf (a missing sample) only in slots >= RSL - 7: the moments pass
+//     needs its `finite ? v : c0` select there alone, and N >= RSL - 7 puts
+//     its one stop (el = round4(N)) at RSL - 4 or RSL.
+// A wave with a lane below that (nulls, a frame's border) takes the run-time
+// slot loops of the G-lane form in a wave-uniform branch.  Either way the
+// record, the moments (same accumulators, same order) and m.y/z/w are what
+// wz_prepare<128, 1> gives.
+template <int RSL>
+__device__ __forceinline__ void wz_prepare1(float (&v)[128], int kept, int N, RankStore<128, 1> &rs, double &W1,
+                                            double &W2, float &c0) {
+#if defined(__HIP_DEVICE_COMPILE__)   // (store_buf / store_full: device code only)
+    constexpr int E = 128, K0 = RSL - 7;
+    static_assert(RSL % 8 == 0 && RSL >= 72 && RSL <= E, "real-slot buckets of rs_pick(128, 1, N)");
+    sort_col<E, 1, RSL>(v, 0);
+    rs.kept = kept;
+    const int ra = kept / 2 - ((kept & 1) ? 0 : 1), rb = kept / 2;
+    const int el = (N + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1);
+    double s1[SGPU_NACC], s2[SGPU_NACC];
+#pragma unroll
+    for (int q = 0; q < SGPU_NACC; q++) s1[q] = s2[q] = 0.0;
+    float sa = 0.f, sb = 0.f;
+    if (__ballot(kept < K0) == 0ull) {
+        rs.store_full<RSL>(v);
+#pragma unroll
+        for (int e = RSL / 2 - 4; e <= RSL / 2; e++) {
+            sa = (e == ra) ? v[e] : sa;
+            sb = (e == rb) ? v[e] : sb;
+        }
+        c0 = median_from(sa, sb, kept);
+        const double cd = (double)c0;
+#pragma unroll
+        for (int e = 0; e < RSL; e++) {
+            if (e == RSL - 4 && el <= RSL - 4) break;
+            const float xe = (e < K0 || v[e] < f_inf()) ? v[e] : c0;
+            const double y = (double)xe - cd;
+            s1[e % SGPU_NACC] += y;
+            s2[e % SGPU_NACC] = fma(y, y, s2[e % SGPU_NACC]);
+        }
+    } else {
+        int kmin = kept;
+#pragma unroll
+        for (int lm = 32; lm >= 1; lm >>= 1) kmin = min(kmin, __shfl_xor(kmin, lm, 64));
+        kmin = __builtin_amdgcn_readfirstlane(kmin);
+        rs.store_buf(v, 0, kmin, N);
+        const int ew0 = kmin / 2 - 1, ew1 = N / 2;
+#pragma unroll
+        for (int e = 0; e <= RSL / 2; e++) {
+            if (e >= ew0 && e <= ew1) {
+                sa = (e == ra) ? v[e] : sa;
+                sb = (e == rb) ? v[e] : sb;
+            }
+        }
+        c0 = median_from(sa, sb, kept);
+        const double cd = (double)c0;
+        const int elim = el < RSL ? el : RSL;
+#pragma unroll
+        for (int e = 0; e < RSL; e++) {
+            SG_STOP4(e, elim);
+            // the sorted column's +Inf are its ranks >= kept; the compare
+            // follows its slot's turn (pinned: 128 of them moved to the front
+            // each held an SGPR pair to its select)
+            int ke = kept;
+            opaque(ke);
+            const float xe = e < ke ? v[e] : c0;
+            const double y = (double)xe - cd;
+            s1[e % SGPU_NACC] += y;
+            s2[e % SGPU_NACC] = fma(y, y, s2[e % SGPU_NACC]);
+        }
+    }
+    W1 = s1[0];
+    W2 = s2[0];
+#pragma unroll
+    for (int q = 1; q < SGPU_NACC; q++) {
+        W1 += s1[q];
+        W2 += s2[q];
+    }
+#endif
+}
+
+template <int NP, int XF, int W, int RSL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
+void k_stack_wz_prep1(KParams p) {
+    static_assert(NP == 128, "one lane per pixel: N <= 128");
+    using RS = RankStore<NP, 1>;
+    const long long loc = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (loc >= p.wz_cnt) return;
+    const long long pix = p.wz_pix0 + loc;
+    int kept = 0, bad = 0;
+    float v[NP];
+    gather_column<XF, NP, 1, true, 0, RSL, SGPU_GATHER_SLOTSTEP, true>(p, v, pix, (int)(pix % p.W), 0, kept, bad);
+    // the NaN / Inf test is settled here: its only reader is the record's
+    // last store, and left to the compiler the detector's chain sinks below
+    // the sort with a copy of every gathered sample alive (104 VGPRs)
+    opaque(bad);
+    RS rs;
+    rs.base = p.wz_ranks;
+    rs.stride = p.wz_cnt;
+    rs.p = loc;
+    double W1, W2;
+    float c0;
+    // a column with a NaN or no sample goes through as well (wave-uniform
+    // code; what it stores stays in its own column of the record, unread)
+    wz_prepare1<RSL>(v, kept, p.nframes, rs, W1, W2, c0);
+    p.wz_mom[loc] = W1;
+    p.wz_mom[p.wz_cnt + loc] = W2;
+    p.wz_mom[2 * p.wz_cnt + loc] = (double)c0;
+    int4 m;
+    m.x = (bad || kept == 0) ? -1 : kept;
+    m.y = rs.hi0;
+    m.z = rs.mid0;
+    m.w = rs.mid1;
+    reinterpret_cast<int4 *>(p.wz_meta)[loc] = m;
 }
 
 // PG (here and in the rounds kernels below): the lanes per pixel of the prep
