@@ -514,6 +514,48 @@ int sgpu_warp_table(int interpolation, float *tab, int *taps);
  * memory (counts[1]). */
 int sgpu_warp_last_tiles(sgpu_context *ctx, long counts[2]);
 
+/* ---- drizzle (seqapplyreg -drizzle) ---------------------------------------- */
+
+/* The arithmetic is the specification in DESIGN.md "Drizzle" (6h), modelled
+ * on cdrizzle's square / turbo / point kernels; parity with Siril is
+ * unpinned. */
+enum { SGPU_DRIZZLE_POINT = 0, SGPU_DRIZZLE_TURBO = 1, SGPU_DRIZZLE_SQUARE = 2 };
+typedef struct {
+	double scale;    /* 0.1 .. 4: output pixels per input pixel */
+	double pixfrac;  /* (0, 1]: the side of the shrunk drop in input pixels */
+	int kernel;      /* SGPU_DRIZZLE_* */
+	int reserved;    /* 0 */
+} sgpu_drizzle_params;
+/* out = (int)floor(size * scale + 0.5) per axis.  A scale outside 0.1 .. 4
+ * or an output dimension below 1 returns SGPU_BAD_ARGUMENT.  Host only. */
+int sgpu_drizzle_output_size(int width, int height, double scale, int *out_w, int *out_h);
+/* The input -> reference maps the drizzle uses, 9 doubles per frame in A:
+ * F * ((Href^-1 * Hf) * F), the map sgpu_warp_inverse_maps inverts, with
+ * its refusals.  Host only. */
+int sgpu_drizzle_forward_maps(int nframes, const double *H, int ref_index, int height, double *A);
+/* The refusals of sgpu_drizzle_frames_device that depend on the frame size:
+ * SGPU_BAD_ARGUMENT when the denominator of a frame's map is zero or changes
+ * sign over the input frame, or that of its inverse over the output frame.
+ * A: as sgpu_drizzle_forward_maps returns it.  Host only. */
+int sgpu_drizzle_check_maps(int nframes, const double *A, int width, int height,
+		const sgpu_drizzle_params *params);
+/* Drizzle nframes device frames (layout as sgpu_shift_frames_device;
+ * elem_size 4: float, 2: WORD taken as (float)v) onto the reference frame's
+ * grid scaled by params->scale: per frame a float image and a float weight
+ * plane of out_w x out_h (sgpu_drizzle_output_size), out_frame_stride floats
+ * apart, both fully overwritten; a pixel nothing landed on is 0 with weight
+ * 0.  d_pixel_weights: width x height floats >= 0 shared by the frames (an
+ * input pixel of weight 0 is skipped), or NULL for 1.  Every output pixel is
+ * the sequential scatter over input pixels in raster order, bit for bit.
+ * Synchronous. */
+int sgpu_drizzle_frames_device(sgpu_context *ctx, const void *d_in, int elem_size, int nframes, int width,
+		int height, long frame_stride, const float *d_pixel_weights, const double *H, int ref_index,
+		const sgpu_drizzle_params *params, float *d_out, float *d_out_weights, long out_frame_stride);
+/* Output tiles of the last sgpu_drizzle_frames_device call that read drops
+ * staged in LDS (counts[0]) and that mapped every candidate themselves
+ * (counts[1]). */
+int sgpu_drizzle_last_tiles(sgpu_context *ctx, long counts[2]);
+
 /* ---- calibration (the `calibrate` command: preprocess()) ------------------ */
 
 /* Arithmetic: the specification in DESIGN.md "Calibration" (S1-S7), restated
@@ -817,6 +859,11 @@ int sgpu_last_timing(sgpu_context *ctx, float ms[2]);
  * params (weights, scale/offset/mul, shiftx, GESD critical values) are sized
  * for that count; sgpu_stack_seq_opts without filter_included stacks every
  * frame, as the reference's `stack` command does.
+ * A regular FITS sequence whose drizzle_flag is set (seqapplyreg -drizzle):
+ * a mean stack reads the rows of drizztmp/oweight_<frame file> beside every
+ * frame with each block and stacks with them as the drizzle weights of
+ * sgpu_stack_rows_planes_device; a missing weight file, or registration
+ * shifts / -maximize on such a sequence, return SGPU_SEQUENCE_ERROR.
  * Returns ST_*. */
 int sgpu_stack_seq(sgpu_context *ctx, const char *seq_path, const sgpu_stack_params *params,
 		int use_registration, int use_32bit_output, const char *out_path, uint64_t counts[2],

@@ -45,6 +45,8 @@ EXPORTS = (
     "sgpu_stack_blocks", "sgpu_feather_mask_size", "sgpu_feather_masks_device", "sgpu_feather_block_area",
     "sgpu_feather_block_device", "sgpu_set_seq_readers", "sgpu_last_seq_stats", "sgpu_release_seq_buffers",
     "sgpu_warp_frames_device", "sgpu_warp_inverse_maps", "sgpu_warp_table", "sgpu_warp_last_tiles",
+    "sgpu_drizzle_output_size", "sgpu_drizzle_forward_maps", "sgpu_drizzle_check_maps",
+    "sgpu_drizzle_frames_device", "sgpu_drizzle_last_tiles",
     "sgpu_region_stats_device", "sgpu_equalize_cfa_flat_device", "sgpu_find_deviant_pixels_device",
     "sgpu_cosmetic_correction_device", "sgpu_dark_optimize_device", "sgpu_calibrate_frames_device",
     "sgpu_star_default_params", "sgpu_match_default_params", "sgpu_star_smooth_table", "sgpu_find_stars_device",
@@ -95,6 +97,11 @@ class PsfParams(C.Structure):
     """sgpu_psf_params (include/sirilgpu.h)."""
     _fields_ = [(f, C.c_double) for f in ("beta", "min_fwhm", "roundness_min", "sat")] + \
         [(f, C.c_int) for f in ("profile", "radius", "max_iter", "reserved")]
+
+
+class DrizzleParams(C.Structure):
+    """sgpu_drizzle_params (include/sirilgpu.h)."""
+    _fields_ = [("scale", C.c_double), ("pixfrac", C.c_double), ("kernel", C.c_int), ("reserved", C.c_int)]
 
 
 class MatchParams(C.Structure):
@@ -344,6 +351,17 @@ def lib():
         L.sgpu_warp_table.argtypes = [i, vp, pi]
         L.sgpu_warp_last_tiles.restype = i
         L.sgpu_warp_last_tiles.argtypes = [vp, C.POINTER(C.c_long)]
+        L.sgpu_drizzle_output_size.restype = i
+        L.sgpu_drizzle_output_size.argtypes = [i, i, C.c_double, pi, pi]
+        L.sgpu_drizzle_forward_maps.restype = i
+        L.sgpu_drizzle_forward_maps.argtypes = [i, vp, i, i, vp]
+        L.sgpu_drizzle_check_maps.restype = i
+        L.sgpu_drizzle_check_maps.argtypes = [i, vp, i, i, C.POINTER(DrizzleParams)]
+        L.sgpu_drizzle_frames_device.restype = i
+        L.sgpu_drizzle_frames_device.argtypes = [vp, vp, i, i, i, i, C.c_long, vp, vp, i, C.POINTER(DrizzleParams),
+                                                 vp, vp, C.c_long]
+        L.sgpu_drizzle_last_tiles.restype = i
+        L.sgpu_drizzle_last_tiles.argtypes = [vp, C.POINTER(C.c_long)]
         pl, pd = C.POINTER(C.c_long), C.POINTER(C.c_double)
         L.sgpu_region_stats_device.restype = i
         L.sgpu_region_stats_device.argtypes = [vp, vp, i, i, i, i, i, i, i, pl, pd, pd]

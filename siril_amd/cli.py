@@ -9,7 +9,13 @@ siril_amd/sequence.py).  Prints the output path and the rejection totals.
 `python -m siril_amd.cli register <seq> [-layer=N] [-transf=shift|similarity|affine|homography] [-minpairs=N]
 [-maxstars=N] [-noout] [-interp=ne|li|cu|ar|la] [-noclamp] [-prefix=r_] [-psf=moments|gaussian|moffat]`: star-based
 global registration (siril_amd/registration.py); rewrites the .seq with the homographies and, unless -noout, writes
-the warped 32-bit <prefix><name>NNNNN.fit and their .seq.  -psf=gaussian|moffat measures the stars with a PSF fit."""
+the warped 32-bit <prefix><name>NNNNN.fit and their .seq.  -psf=gaussian|moffat measures the stars with a PSF fit.
+
+`python -m siril_amd.cli seqapplyreg <seq> [-layer=N] [-prefix=r_] [-interp=ne|li|cu|ar|la] [-noclamp]` applies the
+homographies `register -noout` wrote, as `register`'s output stage does; `seqapplyreg <seq> -drizzle [-scale=1]
+[-pixfrac=1] [-kernel=point|turbo|square] [-flat=FILE] [-layer=N] [-prefix=r_]` drizzles the frames instead: 32-bit
+<prefix><name>NNNNN.fit of the scaled size, their weight planes in drizztmp/oweight_<prefix><name>NNNNN.fit, and a
+.seq with the drizzle flag set."""
 import sys
 import time
 
@@ -29,6 +35,14 @@ def main(argv=None):
         out, _, info = run_register(argv)
         print(f"Registered to {out} in {time.perf_counter() - t0:.3f} s; {int(info['registered'].sum())} of "
               f"{len(info['registered'])} frames, pairs " + " ".join(str(int(v)) for v in info["npairs"]))
+        return 0
+    if argv and argv[0] == "seqapplyreg":
+        from siril_amd.registration import run_seqapplyreg
+        t0 = time.perf_counter()
+        out, _, info = run_seqapplyreg(argv)
+        print(f"Applied registration to {out} in {time.perf_counter() - t0:.3f} s; "
+              f"{int(info['registered'].sum())} of {len(info['registered'])} frames" +
+              (f", drizzled to {info['size'][0]} x {info['size'][1]}" if "size" in info else ""))
         return 0
     if not argv or argv[0] != "stack":
         print(__doc__, file=sys.stderr)

@@ -132,6 +132,10 @@ struct sgpu_context {
     sgpu_host::DevBuf warp_ws;
     std::vector<double> h_warp;
     unsigned long long warp_tiles[2] = {0, 0};   // last call: staged, direct
+    // drizzle: tile counters and per-frame forward / inverse maps (one device block and its host image)
+    sgpu_host::DevBuf drz_ws;
+    std::vector<double> h_drz;
+    unsigned long long drz_tiles[2] = {0, 0};    // last call: staged, direct
     // calibration: row sums / results of the region statistics, dark-optimisation
     // factors, compaction counters, and the cosmetic-correction launch plan
     sgpu_host::DevBuf cal_rows, cal_k, cal_cnt, cal_plan;
@@ -154,7 +158,7 @@ struct sgpu_context {
                                      &dft_tw, &dft_ref, &dft_t1, &dft_t2, &dft_best, &dft_shifts,
                                      &dft_frames, &rl_u, &rl_e, &rl_f, &rl_r, &rl_w, &rl_taps, &rl_small,
                                      &rl_io, &rl_reg, &rl_gxy, &rlf_t1, &rlf_t2, &rlf_ka, &rlf_kb, &rlf_kt, &rlf_tw1, &rlf_tw2, &dm_ws, &dm_mm, &dm_io, &ns_state, &ns_hist, &ns_part, &ns_io, &bn_rows, &qe_buf, &qe_part, &qe_io, &onorm, &ov_ws, &ov_tab,
-                                     &fb2_list, &fb2_count, &wz_ws, &wz_cnt, &fe_tab, &fe_dt, &cfa_tmp, &cstripe, &warp_ws, &cal_rows, &cal_k, &cal_cnt, &cal_plan,
+                                     &fb2_list, &fb2_count, &wz_ws, &wz_cnt, &fe_tab, &fe_dt, &cfa_tmp, &cstripe, &warp_ws, &drz_ws, &cal_rows, &cal_k, &cal_cnt, &cal_plan,
                                      &star_tc, &star_slots, &star_fp, &star_out, &psf_jobs, &psf_out,
                                      &seq_in[0], &seq_in[1], &seq_out, &seq_lo, &seq_hi, &seq_cnt})
             b->release();

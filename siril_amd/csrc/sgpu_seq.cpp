@@ -650,6 +650,7 @@ struct Seq {
     std::vector<double> quality[kLayers];
     std::vector<int> nstars[kLayers];
     bool has_reg[kLayers] = {false};
+    bool drizzle = false;             // drizzle_flag: the frames' weight planes lie in drizztmp/ (seqapplyreg -drizzle)
 };
 
 int round_to_int(double x) {        // core/proto.h:208-213
@@ -680,8 +681,9 @@ int read_seq(const char *path, Seq &q) {
             const int nt = std::sscanf(line + 2, fmt, name, &q.beg, &q.number, &q.selnum, &q.fixed,
                                        &q.reference, &q.version, &var, &fz, &dz);
             if (nt < 6 || q.number < 1) { err = fail(SGPU_SEQUENCE_ERROR, "bad S line"); break; }
-            if (var || fz || dz) { err = fail(SGPU_SEQUENCE_ERROR, "variable/fz/drizzle sequences not supported"); break; }
+            if (var || fz) { err = fail(SGPU_SEQUENCE_ERROR, "variable/fz/drizzle sequences not supported"); break; }
             q.name = name;
+            q.drizzle = dz != 0;
             q.filenum.assign(q.number, 0);
             q.incl.assign(q.number, 0);
             for (int l = 0; l < Seq::kLayers; l++) {
@@ -753,6 +755,7 @@ int read_seq(const char *path, Seq &q) {
     std::fclose(fp);
     if (err) return err;
     if (!have_s || ni != q.number) return fail(SGPU_SEQUENCE_ERROR, "sequence file incomplete");
+    if (q.drizzle && q.type) return fail(SGPU_SEQUENCE_ERROR, "variable/fz/drizzle sequences not supported");
     return SGPU_OK;
 }
 
@@ -812,6 +815,12 @@ std::string frame_path(const Seq &q, int filenum) {
         }
     }
     return q.dir + q.name + num + ".fit";
+}
+
+// the weight plane seqapplyreg -drizzle wrote for a frame: drizztmp/oweight_<frame file> beside it
+std::string drizzle_weight_path(const Seq &q, int filenum) {
+    const std::string fp = frame_path(q, filenum);
+    return q.dir + "drizztmp/oweight_" + fp.substr(q.dir.size());
 }
 
 // the frames of a sequence, in sequence order (io/seqfile.c:426-485)
@@ -1543,6 +1552,28 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
     // planes of stack_read_block_data (median_and_mean.c:483-525), which
     // depend on Siril's block plan (stack_compute_parallel_blocks)
     const bool feather = O.feather > 0 && p.method == SGPU_METHOD_MEAN;
+    // drizzled sequences (drizzle_flag, mean stacks): the matching rows of every
+    // frame's weight plane are read with each block and go to the stack as
+    // its drizzle weights; median stacks ignore them
+    const bool drizzled = q.drizzle && p.method == SGPU_METHOD_MEAN;
+    std::vector<Img> wfr;
+    if (drizzled) {
+        if (maximize || any_x) return fail(SGPU_SEQUENCE_ERROR, "a drizzled sequence is stacked without shifts");
+        for (int k = 0; k < N; k++)
+            if (shifty[k]) return fail(SGPU_SEQUENCE_ERROR, "a drizzled sequence is stacked without shifts");
+        wfr.resize(N);
+        for (int k = 0; k < N; k++) {
+            const std::string wp = drizzle_weight_path(q, q.filenum[idx[k]]);
+            FILE *fp = std::fopen(wp.c_str(), "rb");
+            if (!fp) return fail(SGPU_SEQUENCE_ERROR, "drizzle weight file missing: " + wp);
+            std::fclose(fp);
+            if (int r = fits_open(wp.c_str(), wfr[k])) return r;
+            if (wfr[k].w != Win || wfr[k].h != Hin || wfr[k].file_bitpix != -32)
+                return fail(SGPU_SEQUENCE_ERROR, "drizzle weight file is not a 32-bit plane of the frames' size: " + wp);
+        }
+    }
+    // both kinds of weight planes stack from device-resident blocks
+    const bool planes = feather || drizzled;
     // row blocks in FITS row order: (first row, rows)
     std::vector<std::pair<long, long>> plan;
     long rows = 0;
@@ -1575,7 +1606,7 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
     } else {
         // block height: N frames of `rows` rows within the budget (two buffers)
         const long budget = max_block_bytes > 0 ? max_block_bytes : (512L << 20);
-        rows = std::max(1L, budget / ((long)N * W * es));
+        rows = std::max(1L, budget / ((long)N * W * (es + (drizzled ? 4 : 0))));
         rows = std::min(rows, H);
         // the first block's read is the one nothing overlaps: a quarter-size
         // first block shortens it (blocks are independent row ranges, the
@@ -1604,6 +1635,9 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
             hb[b] = (unsigned char *)ctx->seq_pin[b].p;
         }
     }
+    std::vector<float> hbw[2];           // drizzle weights of a block, frame-major like the samples
+    if (drizzled)
+        for (int b = 0; b < 2; b++) hbw[b].resize((size_t)N * rows * W);
     int read_err[2] = {0, 0};
     // frames of a block are read by a pool of host threads (file reads + byte
     // swaps): the context's setting, else OMP_NUM_THREADS, else 8 (at most 64)
@@ -1629,6 +1663,8 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
                     errs[t] = read_rows(fr[k], layer, r0 - shifty[k], nr, rows_in.data(), tmp, READ_PARTIAL);
                     if (!errs[t]) place_rows(rows_in.data(), Win, dst, W, nr, shiftx[k], es);
                 }
+                if (drizzled && !errs[t])
+                    errs[t] = read_rows(wfr[k], 0, r0, nr, hbw[slot].data() + (size_t)k * nr * W, tmp, READ_RAW);
             }
         };
         std::vector<std::thread> pool;
@@ -1682,26 +1718,30 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
             for (void *q : p) (void)hipFree(q);
         }
     } dev;
-    float *d_masks = nullptr, *d_planes = nullptr;
+    float *d_masks = nullptr, *d_planes = nullptr, *d_drz = nullptr;
     unsigned char *d_blk = nullptr, *d_out = nullptr;
     uint16_t *d_lo = nullptr, *d_hi = nullptr;
     uint64_t *d_cnt = nullptr;
     std::vector<int> shifty_ref, placex;
-    if (feather) {
+    if (planes) {
         HIP_TRY(hipSetDevice(ctx->device));
-        long mw = 0, mh = 0;
-        sgpu_feather_mask_size(Win, Hin, &mw, &mh);
-        if (mw < 1 || mh < 1) return fail(SGPU_BAD_ARGUMENT, "-feather= needs frames of at least 10x10 pixels");
-        d_masks = (float *)dev.get((size_t)N * mw * mh * sizeof(float));
-        d_planes = (float *)dev.get((size_t)N * rows * W * sizeof(float));
         d_blk = (unsigned char *)dev.get(blk);
         d_out = (unsigned char *)dev.get((size_t)rows * W * 4);
         d_lo = (uint16_t *)dev.get((size_t)rows * W * 2);
         d_hi = (uint16_t *)dev.get((size_t)rows * W * 2);
         d_cnt = (uint64_t *)dev.get(2 * sizeof(uint64_t));
-        if (!d_masks || !d_planes || !d_blk || !d_out || !d_lo || !d_hi || !d_cnt)
-            return fail(SGPU_ALLOC_ERROR, "hipMalloc failed (feathering)");
+        if (drizzled) d_drz = (float *)dev.get((size_t)N * rows * W * sizeof(float));
+        if (!d_blk || !d_out || !d_lo || !d_hi || !d_cnt || (drizzled && !d_drz))
+            return fail(SGPU_ALLOC_ERROR, "hipMalloc failed (weight planes)");
         HIP_TRY(hipMemset(d_cnt, 0, 2 * sizeof(uint64_t)));
+    }
+    if (feather) {
+        long mw = 0, mh = 0;
+        sgpu_feather_mask_size(Win, Hin, &mw, &mh);
+        if (mw < 1 || mh < 1) return fail(SGPU_BAD_ARGUMENT, "-feather= needs frames of at least 10x10 pixels");
+        d_masks = (float *)dev.get((size_t)N * mw * mh * sizeof(float));
+        d_planes = (float *)dev.get((size_t)N * rows * W * sizeof(float));
+        if (!d_masks || !d_planes) return fail(SGPU_ALLOC_ERROR, "hipMalloc failed (feathering)");
         // compute_mask_image_hook: the green layer of colour frames, else the
         // first, of every whole frame (readfits order = FITS rows)
         const int mlayer = NL == 3 ? 1 : 0;
@@ -1746,7 +1786,7 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
     bool used[2] = {false, false};
     double h2d_ms = 0.0, kern_ms = 0.0, h2d_bytes = 0.0;
     int nblocks = 0;
-    if (!feather) {
+    if (!planes) {
         HIP_TRY(hipSetDevice(ctx->device));
         HIP_TRY(hipStreamCreateWithFlags(&pp.cs, hipStreamNonBlocking));
         for (int b = 0; b < 2; b++) {
@@ -1807,7 +1847,7 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
                 break;
             }
             std::thread reader;
-            if (!feather) {
+            if (!planes) {
                 // H2D of this block on the copy stream, after the stack that
                 // last read the device buffer
                 const size_t nbytes = (size_t)N * nr * W * es;
@@ -1828,22 +1868,27 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
             if (b + 1 < plan.size()) reader = std::thread(read_block, slot ^ 1, l, plan[b + 1].first, plan[b + 1].second);
             const size_t o = l * plane + (size_t)r0 * W;
             uint16_t *lo = rejmaps ? rlo.data() + o : nullptr, *hi = rejmaps ? rhi.data() + o : nullptr;
-            if (feather) {
+            if (planes) {
                 const size_t n = (size_t)nr * W;
-                rc = sgpu_feather_block_device(ctx, d_masks, N, Win, Hin, H - r0 - nr, nr,
-                                               shifty_ref.empty() ? nullptr : shifty_ref.data(),
-                                               placex.empty() ? nullptr : placex.data(), W, (float)O.feather, 1,
-                                               d_planes, (long)n);
+                if (feather)
+                    rc = sgpu_feather_block_device(ctx, d_masks, N, Win, Hin, H - r0 - nr, nr,
+                                                   shifty_ref.empty() ? nullptr : shifty_ref.data(),
+                                                   placex.empty() ? nullptr : placex.data(), W, (float)O.feather, 1,
+                                                   d_planes, (long)n);
+                if (!rc && drizzled &&
+                    hipMemcpyAsync(d_drz, hbw[slot].data(), (size_t)N * n * sizeof(float), hipMemcpyHostToDevice,
+                                   ctx->stream) != hipSuccess)
+                    rc = fail(SGPU_NO_DEVICE, "hipMemcpy failed (drizzle weights)");
                 if (!rc && hipMemcpyAsync(d_blk, hb[slot], (size_t)N * n * es, hipMemcpyHostToDevice,
                                           ctx->stream) != hipSuccess)
                     rc = fail(SGPU_NO_DEVICE, "hipMemcpy failed (feathering)");
                 if (!rc && u16)
-                    rc = sgpu_stack_rows_u16_planes_device(ctx, (const uint16_t *)d_blk, nullptr, d_planes, N, W, nr,
+                    rc = sgpu_stack_rows_u16_planes_device(ctx, (const uint16_t *)d_blk, d_drz, d_planes, N, W, nr,
                                                            (long)n, &pl, out32 ? (float *)d_out : nullptr,
                                                            out32 ? nullptr : (uint16_t *)d_out, rejmaps ? d_lo : nullptr,
                                                            rejmaps ? d_hi : nullptr, d_cnt);
                 else if (!rc)
-                    rc = sgpu_stack_rows_planes_device(ctx, (const float *)d_blk, nullptr, d_planes, N, W, nr, (long)n,
+                    rc = sgpu_stack_rows_planes_device(ctx, (const float *)d_blk, d_drz, d_planes, N, W, nr, (long)n,
                                                        &pl, (float *)d_out, rejmaps ? d_lo : nullptr,
                                                        rejmaps ? d_hi : nullptr, d_cnt);
                 if (!rc) {

@@ -335,6 +335,100 @@ def warp_frames(frames, Hs, ref_index: int, interpolation: int = OPENCV_LANCZOS4
     return out
 
 
+# ---- drizzle (seqapplyreg -drizzle) -----------------------------------------
+DRIZZLE_KERNELS = {"point": 0, "turbo": 1, "square": 2}
+
+
+def _drizzle_params(scale, pixfrac, kernel):
+    from ._lib import DrizzleParams
+    if isinstance(kernel, str):
+        if kernel.lower() not in DRIZZLE_KERNELS:
+            raise ValueError(f"drizzle kernel {kernel!r}: point, turbo or square")
+        kernel = DRIZZLE_KERNELS[kernel.lower()]
+    return DrizzleParams(float(scale), float(pixfrac), int(kernel), 0)
+
+
+def drizzle_output_size(width: int, height: int, scale: float) -> tuple:
+    """(out_w, out_h) = floor(size * scale + 0.5) per axis
+    (sgpu_drizzle_output_size); a scale outside 0.1 .. 4 or an output
+    dimension below 1 raises SgpuError."""
+    ow, oh = C.c_int(0), C.c_int(0)
+    check(lib().sgpu_drizzle_output_size(int(width), int(height), float(scale), C.byref(ow), C.byref(oh)),
+          "sgpu_drizzle_output_size")
+    return ow.value, oh.value
+
+
+def drizzle_forward_maps(Hs, ref_index: int, height: int, width: Optional[int] = None, scale: float = 1.0,
+                         pixfrac: float = 1.0, kernel="square") -> np.ndarray:
+    """The input -> reference maps drizzle_frames uses ([N, 9] float64):
+    F * ((Href^-1 * Hf) * F), F the row flip of a `height`-row frame
+    (sgpu_drizzle_forward_maps).  Singular or non-finite maps raise SgpuError.
+    With `width` the refusals that depend on the frame size are checked too
+    (sgpu_drizzle_check_maps): a denominator that vanishes or changes sign
+    over the input frame, or the inverse map's over the output frame."""
+    H = np.ascontiguousarray(np.asarray(Hs, np.float64).reshape(-1, 9))
+    A = np.zeros_like(H)
+    check(lib().sgpu_drizzle_forward_maps(H.shape[0], H.ctypes.data_as(C.c_void_p), int(ref_index), int(height),
+                                          A.ctypes.data_as(C.c_void_p)), "sgpu_drizzle_forward_maps")
+    if width is not None:
+        p = _drizzle_params(scale, pixfrac, kernel)
+        check(lib().sgpu_drizzle_check_maps(A.shape[0], A.ctypes.data_as(C.c_void_p), int(width), int(height),
+                                            C.byref(p)), "sgpu_drizzle_check_maps")
+    return A
+
+
+def drizzle_last_tiles(ctx) -> tuple:
+    """(staged, direct): output tiles of ctx's last drizzle_frames call that
+    read drops staged in LDS, and that mapped every candidate themselves."""
+    cnt = (C.c_long * 2)()
+    check(lib().sgpu_drizzle_last_tiles(ctx.h, cnt), "sgpu_drizzle_last_tiles")
+    return int(cnt[0]), int(cnt[1])
+
+
+def drizzle_frames(frames, Hs, ref_index: int, scale: float = 1.0, pixfrac: float = 1.0, kernel="square",
+                   pixel_weights=None, out=None, out_weights=None, ctx=None):
+    """Drizzle frames [N, H, W] (CUDA tensor, float32 or 16-bit WORD storage
+    taken as (float)v) through Href^-1 * Hf onto the reference grid scaled by
+    `scale` (0.1 .. 4), each input pixel shrunk to `pixfrac` (0 < pixfrac <= 1)
+    of its side, with the "square", "turbo" or "point" kernel.  pixel_weights:
+    [H, W] float32 CUDA tensor of weights >= 0 shared by the frames (0 skips
+    the pixel), or None.  Returns (image, weights): float32 [N, out_h, out_w]
+    each, fully overwritten; a pixel nothing landed on is 0 with weight 0, and
+    `weights` is what Context.stack(drizzle=) takes.  The arithmetic is the
+    specification in DESIGN.md "Drizzle" (Siril parity unpinned)."""
+    import torch
+    from .stacking import Context
+    ctx = ctx or Context(frames.device.index or 0)
+    if frames.dim() != 3 or not frames.is_cuda or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous CUDA tensor [N, H, W]")
+    if frames.element_size() not in (2, 4) or (frames.element_size() == 4 and frames.dtype != torch.float32):
+        raise ValueError("frames must be float32 or 16-bit WORD storage")
+    n, h, w = frames.shape
+    H = np.ascontiguousarray(np.asarray(Hs, np.float64).reshape(n, 9))
+    p = _drizzle_params(scale, pixfrac, kernel)
+    ow, oh = drizzle_output_size(w, h, p.scale)
+    pwp = None
+    if pixel_weights is not None:
+        if (not pixel_weights.is_cuda or pixel_weights.dtype != torch.float32 or tuple(pixel_weights.shape) != (h, w)
+                or not pixel_weights.is_contiguous() or pixel_weights.device != frames.device):
+            raise ValueError("pixel_weights must be a contiguous float32 CUDA tensor [H, W] on the frames' device")
+        pwp = C.c_void_p(pixel_weights.data_ptr())
+    planes = []
+    for t, name in ((out, "out"), (out_weights, "out_weights")):
+        if t is None:
+            t = torch.empty((n, oh, ow), dtype=torch.float32, device=frames.device)
+        if (tuple(t.shape) != (n, oh, ow) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                or t.device != frames.device):
+            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor [{n}, {oh}, {ow}]")
+        planes.append(t)
+    ctx.set_stream(torch.cuda.current_stream(frames.device).cuda_stream)
+    check(lib().sgpu_drizzle_frames_device(ctx.h, C.c_void_p(frames.data_ptr()), frames.element_size(), n, w, h, h * w,
+                                           pwp, H.ctypes.data_as(C.c_void_p), int(ref_index), C.byref(p),
+                                           C.c_void_p(planes[0].data_ptr()), C.c_void_p(planes[1].data_ptr()),
+                                           oh * ow), "sgpu_drizzle_frames_device")
+    return planes[0], planes[1]
+
+
 # ---- star detection and star-based global registration ---------------------
 # sgpu_star (include/sirilgpu.h)
 STAR_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("flux", "f8"), ("amp", "f8"), ("fwhm_major", "f8"),
@@ -718,6 +812,58 @@ def _seq_reference(path: str) -> int:
     raise ValueError(f"{path}: no S line")
 
 
+def _frame_io(d, name, fixed, layer, dev):
+    """(read, upload) of a regular FITS sequence: read(num) gives one frame's
+    plane (layer `layer` of RGB frames), upload(host) a device tensor (WORD
+    frames as 16-bit storage)."""
+    import os
+    import torch
+    from .sequence import frame_name, read_fits
+
+    def read(num):
+        a = read_fits(os.path.join(d, frame_name(name, num, fixed)))
+        if a.ndim == 3:
+            if layer >= a.shape[0]:
+                raise ValueError("-layer= is outside the frames' layers")
+            a = a[layer]
+        elif layer:
+            raise ValueError("-layer= is outside the frames' layers")
+        return np.ascontiguousarray(a)
+
+    def upload(host):
+        return torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(dev)
+
+    return read, upload
+
+
+def _write_warped(d, name, fixed, nums, read, upload, good, ref_index, Hs, interp, clamp, prefix, batch, regdata,
+                  layer, ctx):
+    """The output stage of `register` and of `seqapplyreg` without -drizzle:
+    the frames `good` warped onto the reference as 32-bit
+    <prefix><name>NNNNN.fit, renumbered consecutively, and their .seq
+    (identity H).  batch: frames of device memory to use.  Returns the .seq."""
+    import os
+    from .calibration import INV_USHRT_MAX
+    from .sequence import frame_name, write_fits, write_seq
+    per = max(1, batch // 2 - 1)                      # input and output frames, and the reference frame's slot
+    for b0 in range(0, len(good), per):
+        part = good[b0:b0 + per]
+        idx = part if ref_index in part else part + [ref_index]
+        t = upload(np.stack([read(nums[f]) for f in idx]))
+        res = warp_frames(t, Hs[idx], idx.index(ref_index), interp, clamp, ctx=ctx).cpu().numpy()
+        for j, f in enumerate(part):
+            a = res[j]
+            if a.dtype != np.float32:                 # WORD frames: [0, 1] units, as 32-bit FITS hold them
+                a = a.view(np.uint16).astype(np.float32) * np.float32(INV_USHRT_MAX)
+            write_fits(os.path.join(d, frame_name(prefix + name, nums[0] + b0 + j, fixed)), a)
+    # the new sequence holds the registered frames only, renumbered from the first image number
+    out_seq = os.path.join(d, prefix + name + ".seq")
+    write_seq(out_seq, prefix + name, len(good), beg=nums[0], fixed=fixed, reference=good.index(ref_index),
+              homographies=np.tile(np.eye(3), (len(good), 1, 1)), reg_layer=layer,
+              **{k: v[good] for k, v in regdata.items()})
+    return out_seq
+
+
 def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
     """Run one `register` command line (a string or its words) on a regular
     FITS sequence: finds the stars of every frame (layer -layer= of RGB
@@ -732,8 +878,8 @@ def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
     last, Hs, info)."""
     import os
     import torch
-    from .calibration import INV_USHRT_MAX, _read_seq
-    from .sequence import frame_name, read_fits, write_fits, write_seq
+    from .calibration import _read_seq
+    from .sequence import write_seq
     from .stacking import Context
     cmd = parse_register_command(line.split() if isinstance(line, str) else line)
     seq = cmd.seq if cmd.seq.endswith(".seq") else cmd.seq + ".seq"
@@ -747,18 +893,7 @@ def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
     ctx = ctx or Context(0)
     dev = torch.device("cuda", ctx.device)
 
-    def read(num):
-        a = read_fits(os.path.join(d, frame_name(name, num, fixed)))
-        if a.ndim == 3:
-            if cmd.layer >= a.shape[0]:
-                raise ValueError("-layer= is outside the frames' layers")
-            a = a[cmd.layer]
-        elif cmd.layer:
-            raise ValueError("-layer= is outside the frames' layers")
-        return np.ascontiguousarray(a)
-
-    def upload(host):
-        return torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(dev)
+    read, upload = _frame_io(d, name, fixed, cmd.layer, dev)
 
     first = read(nums[0])
     h, w = first.shape
@@ -794,20 +929,202 @@ def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
     if cmd.noout:
         return seq, Hs, info
     good = [f for f in range(n) if reg[f]]
-    per = max(1, batch // 2 - 1)                      # input and output frames, and the reference frame's slot
+    out_seq = _write_warped(d, name, fixed, nums, read, upload, good, ref_index, Hs, cmd.interp, cmd.clamp, cmd.prefix,
+                            batch, regdata, cmd.layer, ctx)
+    return out_seq, Hs, info
+
+
+# ---- seqapplyreg: apply an existing registration, by warp or by drizzle ------
+class SeqApplyRegCommand:
+    """Parsed `seqapplyreg` command."""
+
+    def __init__(self, seq: str):
+        self.seq = seq
+        self.layer = 0
+        self.drizzle = False
+        self.scale = 1.0
+        self.pixfrac = 1.0
+        self.kernel = "square"
+        self.flat = None
+        self.interp = OPENCV_LANCZOS4
+        self.clamp = True
+        self.prefix = "r_"
+
+
+def parse_seqapplyreg_command(words) -> SeqApplyRegCommand:
+    """`seqapplyreg <seq> [-layer=] [-prefix=r_] [-interp=ne|li|cu|ar|la]
+    [-noclamp] | -drizzle [-scale=1] [-pixfrac=1] [-kernel=point|turbo|square]
+    [-flat=FILE]`.  The drizzle options need -drizzle, and -drizzle takes no
+    interpolation."""
+    words = list(words)
+    if words and words[0] == "seqapplyreg":
+        words = words[1:]
+    if not words or words[0].startswith("-"):
+        raise ValueError("seqapplyreg needs a sequence name")
+    cmd = SeqApplyRegCommand(words[0])
+    drizzle_only, warp_only = [], []
+    for o in words[1:]:
+        if o == "-drizzle":
+            cmd.drizzle = True
+        elif o.startswith("-layer="):
+            cmd.layer = int(o[7:])
+            if cmd.layer < 0:
+                raise ValueError("-layer= must not be negative")
+        elif o.startswith("-scale="):
+            cmd.scale = float(o[7:])
+            if not 0.1 <= cmd.scale <= 4.0:
+                raise ValueError("-scale= must be between 0.1 and 4")
+            drizzle_only.append(o)
+        elif o.startswith("-pixfrac="):
+            cmd.pixfrac = float(o[9:])
+            if not 0.0 < cmd.pixfrac <= 1.0:
+                raise ValueError("-pixfrac= must be above 0 and at most 1")
+            drizzle_only.append(o)
+        elif o.startswith("-kernel="):
+            if o[8:] not in DRIZZLE_KERNELS:
+                raise ValueError(f"Unknown drizzle kernel {o[8:]}, aborting.")
+            cmd.kernel = o[8:]
+            drizzle_only.append(o)
+        elif o.startswith("-flat="):
+            cmd.flat = o[6:]
+            if not cmd.flat:
+                raise ValueError("Missing file name after -flat=")
+            drizzle_only.append(o)
+        elif o.startswith("-interp="):
+            if o[8:] not in INTERPOLATIONS:
+                raise ValueError(f"Unknown interpolation {o[8:]}, aborting.")
+            cmd.interp = INTERPOLATIONS[o[8:]]
+            warp_only.append(o)
+        elif o == "-noclamp":
+            cmd.clamp = False
+            warp_only.append(o)
+        elif o.startswith("-prefix="):
+            cmd.prefix = o[8:]
+            if not cmd.prefix:
+                raise ValueError("Missing prefix after -prefix=")
+        else:
+            raise ValueError(f"Unexpected argument to seqapplyreg `{o}', aborting.")
+    if drizzle_only and not cmd.drizzle:
+        raise ValueError(f"{drizzle_only[0]} needs -drizzle")
+    if warp_only and cmd.drizzle:
+        raise ValueError(f"{warp_only[0]} does not apply to -drizzle")
+    return cmd
+
+
+def read_seq_registration(path: str, layer: int = 0):
+    """The registration a .seq holds for `layer`, as write_seq(homographies=)
+    wrote it: (included [n] bool, Hs [n, 3, 3] with the null homography for a
+    frame that is not registered, values) with values the per-frame fwhm,
+    wfwhm, roundness, quality, bkg (float64) and nstars (int32).  ValueError
+    when the file has no R<layer> lines with homographies or not one per
+    image."""
+    inc, rows = [], []
+    tag = f"R{layer}"
+    with open(path) as f:
+        for line in f:
+            t = line.split()
+            if not t:
+                continue
+            if t[0] == "I":
+                inc.append(bool(int(t[2])))
+            elif t[0] == tag:
+                if len(t) != 17 or t[7] != "H":
+                    raise ValueError(f"{path}: an {tag} line without a homography")
+                rows.append([float(v) for v in t[1:7]] + [float(v) for v in t[8:17]])
+    if not rows or len(rows) != len(inc):
+        raise ValueError(f"{path}: no registration data for layer {layer}")
+    r = np.array(rows, np.float64)
+    values = dict(fwhm=r[:, 0], wfwhm=r[:, 1], roundness=r[:, 2], quality=r[:, 3], bkg=r[:, 4],
+                  nstars=r[:, 5].astype(np.int32))
+    return np.array(inc, bool), r[:, 6:].reshape(-1, 3, 3), values
+
+
+def drizzle_flat_weights(flat: np.ndarray) -> np.ndarray:
+    """The pixel-weight plane of a master flat: every sample as
+    a double over the double mean of all samples, rounded to float32; a sample
+    that is not above 0 or not finite weighs 0.  ValueError when the mean is
+    not above 0."""
+    f = np.asarray(flat).astype(np.float64)
+    m = float(np.sum(f, dtype=np.float64)) / f.size
+    if not (m > 0.0 and np.isfinite(m)):
+        raise ValueError("the flat's mean must be above 0")
+    w = (f / m).astype(np.float32)
+    w[~(np.isfinite(w) & (f > 0.0))] = 0.0
+    return w
+
+
+def run_seqapplyreg(line, ctx=None, max_batch_bytes: int = 1 << 30):
+    """Run one `seqapplyreg` command line (a string or its words) on a regular
+    FITS sequence that `register -noout` registered: the included frames with
+    a non-null homography are applied onto the reference frame.  Without
+    -drizzle they are warped exactly as `register`'s output stage does.  With
+    -drizzle they are drizzled (drizzle_frames) to 32-bit
+    <prefix><name>NNNNN.fit of the scaled size (WORD input in [0, 1] units),
+    their weight planes go to drizztmp/oweight_<prefix><name>NNNNN.fit beside
+    them, and the new .seq (identity H, registration values carried over)
+    has its drizzle_flag set.  -flat= weights the input pixels by a master
+    flat over its mean.  Returns (path of the new .seq, Hs, info)."""
+    import os
+    import torch
+    from .calibration import INV_USHRT_MAX, _master_file, _read_seq
+    from .sequence import frame_name, write_fits, write_seq
+    from .stacking import Context
+    cmd = parse_seqapplyreg_command(line.split() if isinstance(line, str) else line)
+    seq = cmd.seq if cmd.seq.endswith(".seq") else cmd.seq + ".seq"
+    d = os.path.dirname(os.path.abspath(seq))
+    name, fixed, nums = _read_seq(seq)
+    if nums != list(range(nums[0], nums[0] + len(nums))):
+        raise ValueError("seqapplyreg needs consecutively numbered images")
+    n = len(nums)
+    inc, Hs, regdata = read_seq_registration(seq, cmd.layer)
+    if len(inc) != n:
+        raise ValueError(f"{seq}: registration data does not match the images")
+    ref_index = _seq_reference(seq)
+    ref_index = ref_index if 0 <= ref_index < n else 0
+    good = [f for f in range(n) if inc[f] and Hs[f].any()]
+    if ref_index not in good:
+        raise ValueError("seqapplyreg: the reference image is not registered")
+    ctx = ctx or Context(0)
+    dev = torch.device("cuda", ctx.device)
+    read, upload = _frame_io(d, name, fixed, cmd.layer, dev)
+    h, w = read(nums[0]).shape
+    info = dict(registered=np.array([f in good for f in range(n)]))
+    if not cmd.drizzle:
+        del regdata["quality"]                        # register carries no quality
+        batch = max(1, int(max_batch_bytes // (h * w * 4)))
+        out_seq = _write_warped(d, name, fixed, nums, read, upload, good, ref_index, Hs, cmd.interp, cmd.clamp,
+                                cmd.prefix, batch, regdata, cmd.layer, ctx)
+        return out_seq, Hs, info
+    ow, oh = drizzle_output_size(w, h, cmd.scale)
+    pw = None
+    if cmd.flat is not None:
+        flat = _master_file(cmd.flat, d)
+        if flat.shape != (h, w):
+            raise ValueError("-flat= does not have the frames' size")
+        pw = torch.from_numpy(drizzle_flat_weights(flat)).to(dev)
+    # device bytes per frame: the input plane and the two output planes of scale^2 its pixels
+    per = max(1, int(max_batch_bytes // (h * w * 4 + 2 * ow * oh * 4)) - 1)   # - 1: the reference frame's slot
+    os.makedirs(os.path.join(d, "drizztmp"), exist_ok=True)
+    tiles = [0, 0]
     for b0 in range(0, len(good), per):
         part = good[b0:b0 + per]
         idx = part if ref_index in part else part + [ref_index]
         t = upload(np.stack([read(nums[f]) for f in idx]))
-        res = warp_frames(t, Hs[idx], idx.index(ref_index), cmd.interp, cmd.clamp, ctx=ctx).cpu().numpy()
+        img, wts = drizzle_frames(t, Hs[idx], idx.index(ref_index), cmd.scale, cmd.pixfrac, cmd.kernel,
+                                  pixel_weights=pw, ctx=ctx)
+        st = drizzle_last_tiles(ctx)
+        tiles = [tiles[0] + st[0], tiles[1] + st[1]]
+        img, wts = img.cpu().numpy(), wts.cpu().numpy()
         for j, f in enumerate(part):
-            a = res[j]
-            if a.dtype != np.float32:                 # WORD frames: [0, 1] units, as 32-bit FITS hold them
-                a = a.view(np.uint16).astype(np.float32) * np.float32(INV_USHRT_MAX)
-            write_fits(os.path.join(d, frame_name(cmd.prefix + name, nums[0] + b0 + j, fixed)), a)
-    # the new sequence holds the registered frames only, renumbered from the first image number
+            a = img[j]
+            if t.dtype != torch.float32:              # WORD frames: [0, 1] units, as 32-bit FITS hold them
+                a = a * np.float32(INV_USHRT_MAX)
+            fn = frame_name(cmd.prefix + name, nums[0] + b0 + j, fixed)
+            write_fits(os.path.join(d, fn), a)
+            write_fits(os.path.join(d, "drizztmp", "oweight_" + fn), wts[j])
     out_seq = os.path.join(d, cmd.prefix + name + ".seq")
     write_seq(out_seq, cmd.prefix + name, len(good), beg=nums[0], fixed=fixed, reference=good.index(ref_index),
-              homographies=np.tile(np.eye(3), (len(good), 1, 1)), reg_layer=cmd.layer,
+              homographies=np.tile(np.eye(3), (len(good), 1, 1)), reg_layer=cmd.layer, drizzle=True,
               **{k: v[good] for k, v in regdata.items()})
+    info.update(tiles=tuple(tiles), size=(ow, oh))
     return out_seq, Hs, info

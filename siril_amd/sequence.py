@@ -175,7 +175,7 @@ def read_frame_rows(path: str, frame: int, layer: int = 0, row0: int = 0, nrows:
 def write_seq(path: str, name: str, number: int, beg: int = 1, fixed: int = 5, reference: int = 0,
               included: Optional[Sequence[bool]] = None, shifts: Optional[Sequence[tuple]] = None,
               kind: Optional[str] = None, nb_layers: int = 1, reg_layer: int = 0, fwhm=None, quality=None,
-              wfwhm=None, roundness=None, bkg=None, nstars=None, homographies=None):
+              wfwhm=None, roundness=None, bkg=None, nstars=None, homographies=None, drizzle: bool = False):
     """Sequence file, version 4 (io/seqfile.c:730-910): S, T (kind "S" SER,
     "F" FITSEQ; None regular FITS), L and I lines, and R<reg_layer> lines with
     the shift-only homography when `shifts` (dx, dy) is given (h02 = dx,
@@ -183,12 +183,14 @@ def write_seq(path: str, name: str, number: int, beg: int = 1, fixed: int = 5, r
     values (fwhm, weighted fwhm, roundness, quality, background, stars;
     seqfile.c:814-829).  `homographies` ([number, 3, 3], top-down as Siril
     stores them) writes all nine entries of every H instead; the null
-    homography (all zeros) marks a frame that is not registered."""
+    homography (all zeros) marks a frame that is not registered.  `drizzle`
+    sets the S line's drizzle_flag: the frames are drizzled and their weight
+    planes lie in drizztmp/ beside them (seqapplyreg -drizzle)."""
     inc = list(included) if included is not None else [True] * number
     lines = ["#Siril sequence file. Contains list of images, selection, registration data and statistics",
              "#S 'sequence_name' start_index nb_images nb_selected fixed_len reference_image version"
              " variable_size fz_flag drizzle_flag",
-             f"S '{name}' {beg} {number} {sum(bool(x) for x in inc)} {fixed} {reference} 4 0 0 0"]
+             f"S '{name}' {beg} {number} {sum(bool(x) for x in inc)} {fixed} {reference} 4 0 0 {int(bool(drizzle))}"]
     if kind:
         lines.append(f"T{kind}")
     lines.append(f"L {nb_layers}")
