@@ -236,6 +236,13 @@ long sgpu_last_exact_pixels(sgpu_context *ctx);
  * work on the stack's own path).  Synchronises the context stream. */
 int sgpu_last_wz_deferred(sgpu_context *ctx, long long out[2]);
 
+/* Float or 16-bit WINSORIZED stacks of more than 64 frames (last launch of
+ * the last stack call): the pixels the moment path handed to the
+ * register-resident sorted kernel (a rank outside the stored ranges, an
+ * undecidable step), summed over the launch's chunks.  Read on request only.
+ * Synchronises the context stream. */
+long sgpu_last_wz_fallback(sgpu_context *ctx);
+
 /* Float NO_REJEC mean (last launch of the last stack call, <= 2^28 pixels):
  * the number of pixels whose float mean the kernel could not prove to be
  * independent of the summation order.  The reference sums kept >= 16 samples

@@ -320,6 +320,24 @@ int sgpu_last_wz_deferred(sgpu_context *c, long long out[2]) {
     return SGPU_OK;
 }
 
+long sgpu_last_wz_fallback(sgpu_context *c) {
+    if (!c) return fail(SGPU_BAD_ARGUMENT, "null context");
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return SGPU_NO_DEVICE;
+    if (c->last_mean || !c->fb2_count.p) return 0;
+    // one list for the launch (fb2_count), or one per chunk (KParams::wz_tcnt:
+    // word 2 k of the counter block, zeroed per launch)
+    int n = 0;
+    if (hipMemcpy(&n, c->fb2_count.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return SGPU_NO_DEVICE;
+    long total = n;
+    if (c->wz_cnt.p) {
+        std::vector<int> t(2 * sgpu::kWzMaxChunks);
+        if (hipMemcpy(t.data(), c->wz_cnt.p, t.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+            return SGPU_NO_DEVICE;
+        for (int k = 0; k < sgpu::kWzMaxChunks; k++) total += t[2 * k];
+    }
+    return total;
+}
+
 long sgpu_last_order_sensitive(sgpu_context *c, int *idx, long cap) {
     if (!c) return fail(SGPU_BAD_ARGUMENT, "null context");
     if (hipStreamSynchronize(c->stream) != hipSuccess) return SGPU_NO_DEVICE;
@@ -499,9 +517,15 @@ int run_launch_body(sgpu_context *c, KParams k, bool has_shift) {
     // (stack_wz.h); SGPU_WZ=0 / 1 / 2 (default) / 3 / 4: off / one kernel /
     // two kernels (prep and rounds overlapped on two streams at N <= 128) /
     // always overlapped / never; SGPU_WZ_RW: the rounds kernel's form (A/B)
-    static const int wz_mode = std::getenv("SGPU_WZ") ? std::atoi(std::getenv("SGPU_WZ")) : 2;
+    // 7: mode 2 with the prep and the capped rounds head fused into one kernel
+    // wherever that kernel exists (float, N = 65..128; every other shape runs
+    // mode 2).  Unset: fused where it measured clearly faster (wz_fused_auto),
+    // mode 2 elsewhere; SGPU_WZ=2 is the two-kernel path everywhere.
+    static const int wz_env = std::getenv("SGPU_WZ") ? std::atoi(std::getenv("SGPU_WZ")) : -1;
+    static const int wz_mode = wz_env < 0 || wz_env == 7 ? 2 : wz_env;
     static const int wz_rw = std::getenv("SGPU_WZ_RW") ? std::atoi(std::getenv("SGPU_WZ_RW")) : 64;
     k.wz_mode = wz_mode;
+    k.wz_fused = wz_env == 7 ? 1 : (wz_env < 0 ? 2 : 0);
     k.wz_rw = wz_rw;
     // NO_REJEC mean (stack_mean.hip): fb2_list collects the pixels whose float
     // mean the kernel cannot prove independent of the summation order

@@ -58,6 +58,8 @@ struct KParams {
     int *wz_tcnt;               // overlapped form: 2 counters per chunk (fb2, fb) + [kWzMaxChunks*2] the total
                                 // of the chunks' exact-kernel pixels, or null (tails after the last chunk)
     int wz_mode;                // 0 register-resident kernel only, 1 moment path in one kernel (LDS), 2 two kernels
+    int wz_fused;               // float, N = 65..128: prep and capped head in one kernel -- 0 never, 1 always (SGPU_WZ=7),
+                                // 2 where it measured faster (SGPU_WZ unset; stack_sorted_inst.h wz_fused_auto)
     int wz_split;               // LDS rounds, float, N <= 128: rounds cap of the head pass (SGPU_WZ_SPLIT; 0: one nest)
     int *wz_scnt;               // split: stripe counters of the two deferral lists [2][kWzStripes * 16], or null
     int *wz_def;                // split: [2] pixels that entered tail pass 1 / 2 (sgpu_last_wz_deferred), or null

@@ -69,6 +69,10 @@
 #ifndef SGPU_WZ_PREP_W128_G1
 #define SGPU_WZ_PREP_W128_G1 3
 #endif
+// the fused prep + rounds kernel (k_stack_wz_fused1): the one-lane prep's budget
+#ifndef SGPU_WZ_FUSED_W128
+#define SGPU_WZ_FUSED_W128 3
+#endif
 // real-slot bounds of the four-lane prep (stack_sorted_rs128.hip): first
 // bound and step; rs_pick_prep4 takes the smallest one >= ceil(N / 4)
 #ifndef SGPU_WZ_PREP4_RS0

@@ -86,6 +86,10 @@ int rs_pick_prep4(int N);
 // 120 in steps of 8 and the full network (rs == 128)
 KernelFn prep1_kernel_128(int xf, int rs);
 int rs_pick_prep1(int N);
+// the fused prep + capped rounds kernel (k_stack_wz_fused1) on the one-lane
+// prep's bounds
+using FusedFn = void (*)(KParams, WzSplit);
+FusedFn fused1_kernel_128(int xf, int rs);
 KernelFn rs_kernel_256(int kind, int xf, int rs);
 KernelFn rs_kernel_512(int kind, int xf, int rs);
 template <int NP> inline KernelFn rs_kernel(int kind, int xf, int rs) {
@@ -117,6 +121,18 @@ inline int wz_exact_block(int N) {
 constexpr int kWzMinChunks = 1;
 constexpr long long kWzMinChunkPix = 1LL << 19;
 
+// Where the fused kernel (k_stack_wz_fused1) is the default: the launches on
+// which it measured clearly faster than the two-kernel path under the rule of
+// DESIGN.md section 8 (every run below every run of the other, medians three
+// ranges apart; profiles/r11_ab_wz_fused.txt): unshifted, unnormalized frames
+// at sigma 3/3 -- N = 100 8.32 -> 7.80 ms, N = 128 11.59 -> 10.67 ms, one
+// rank's 500-row band 1.54 -> 1.44 ms.  Shifted frames (11.01 -> 11.12 ms)
+// and sigma 2/2 (30.6 -> 32.8 ms: four pixels in five outlast the head, and
+// the tails then run beside nothing) measured slower and keep the two
+// kernels, as does every sigma below 3 (not measured; larger sigmas defer
+// less than 3/3).  SGPU_WZ=7 fuses wherever the kernel exists.
+inline bool wz_fused_auto(const KParams &p) { return !p.shiftx && p.sig0 >= 3.f && p.sig1 >= 3.f; }
+
 template <int NP, int G, int RT, int W, int U16 = 0>
 static int launch_one(const KParams &p, hipStream_t s) {
     const long long threads = p.npix * (long long)G;
@@ -147,7 +163,13 @@ static int launch_one(const KParams &p, hipStream_t s) {
             // SGPU_WZ=2 (default): overlapped at NP <= 128 (config 2: 16.13 ->
             // 15.81 ms), one stream above (NP = 512: 52.4 vs 53.2 ms, twice
             // the chunks of 0.9 M pixels); 3: always overlapped; 4: never.
-            const bool ovl = p.wz_mode == 3 || (p.wz_mode == 2 && NP <= 128);
+            // Fused (float, NP = 128, one-lane prep, LDS rounds): one kernel does
+            // the prep and the capped head; one stream and one workspace
+            // buffer per chunk -- fused kernel, tail passes, rounds[b] -- the
+            // chunk's fallbacks on the third stream as below.
+            const bool fused = NP == 128 && !U16 && PG == 1 && p.wz_mode == 2 && p.wz_rw == 64 &&
+                               (p.wz_fused == 1 || (p.wz_fused == 2 && wz_fused_auto(p)));
+            const bool ovl = !fused && (p.wz_mode == 3 || (p.wz_mode == 2 && NP <= 128));
             const int nbuf = ovl ? 2 : 1;
             constexpr int R = RankStore<NP, PG>::R;
             constexpr int PE = NP / PG;
@@ -177,6 +199,7 @@ static int launch_one(const KParams &p, hipStream_t s) {
             if (ch <= 0) return 1;
             WzAux *aux = nullptr;
             hipStream_t sp = s;                      // the prep kernels' stream
+            if (fused && wz_aux(aux)) return -1;     // (the third stream and rounds[])
             if (ovl) {
                 if (wz_aux(aux)) return -1;
                 sp = aux->s2;
@@ -193,7 +216,7 @@ static int launch_one(const KParams &p, hipStream_t s) {
             const int et = wz_exact_block(p.nframes);
             // (16-bit: the tails run after the last chunk -- the LDS exact
             // kernel of the per-chunk form is the float one)
-            const bool tails = !U16 && ovl && p.wz_tcnt && nch <= kWzMaxChunks && et > 0 && p.wz_rw != 100;
+            const bool tails = !U16 && (ovl || fused) && p.wz_tcnt && nch <= kWzMaxChunks && et > 0 && p.wz_rw != 100;
             auto place = [&](int b) {
                 char *base = (char *)p.wz_ws + (long long)b * wsb;
                 q.wz_ranks = (float *)base;
@@ -217,6 +240,10 @@ static int launch_one(const KParams &p, hipStream_t s) {
                 const int prs = rs_pick(PE, PG, p.nframes);
                 if (prs < PE) prep_rs = rs_kernel<NP>(0, p.shiftx ? 1 : 0, prs);
             }
+            FusedFn fused_fn = nullptr;
+            if constexpr (NP == 128 && !U16 && PG == 1) {
+                if (fused && !(fused_fn = fused1_kernel_128(p.shiftx ? 1 : 0, rs_pick_prep1(p.nframes)))) return -1;
+            }
             int k = 0;
             for (long long p0 = 0; p0 < p.npix; p0 += ch, k++) {
                 const int b = k % nbuf;
@@ -232,7 +259,9 @@ static int launch_one(const KParams &p, hipStream_t s) {
                 const unsigned g1 = (unsigned)((q.wz_cnt * PG + 255) / 256), g2 = (unsigned)((q.wz_cnt + 255) / 256);
                 // the buffer's previous chunk must be through its rounds
                 if (ovl && k >= nbuf && hipStreamWaitEvent(sp, aux->rounds[b], 0) != hipSuccess) return -1;
-                if (prep_rs) {
+                if (fused) {
+                    // (no prep launch: the head's slot below launches the fused kernel)
+                } else if (prep_rs) {
                     if (!launch_fn(prep_rs, g1, 256, sp, q)) return -1;
                 } else if constexpr (kOwnPrep) {
                     return -1;                       // (prep4_kernel_128 / prep1_kernel_128 hold the full network too)
@@ -286,7 +315,15 @@ static int launch_one(const KParams &p, hipStream_t s) {
                                         hipSuccess)
                                         return -1;
                                 }
-                                hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP, 0, PG>), dim3(nblk), 64, 0, s, q, sp);
+                                if (fused) {
+                                    KParams qa = q;
+                                    WzSplit spa = sp;
+                                    void *args[] = {&qa, &spa};
+                                    if (hipLaunchKernel((const void *)fused_fn, dim3((nblk + 3) / 4), dim3(256), args, 0, s) !=
+                                        hipSuccess)
+                                        return -1;
+                                } else
+                                    hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP, 0, PG>), dim3(nblk), 64, 0, s, q, sp);
                                 for (int pass = 0; sp.cap && pass < SGPU_WZ_TAIL_PASSES; pass++) {
                                     sp.list_in = lists[pass & 1];
                                     sp.cnt_in = p.wz_scnt + (pass & 1) * kWzStripes * kWzStripeStep;
@@ -305,7 +342,7 @@ static int launch_one(const KParams &p, hipStream_t s) {
                     }
                 }
                 if (hipGetLastError() != hipSuccess) return -1;
-                if (ovl && hipEventRecord(aux->rounds[b], s) != hipSuccess) return -1;
+                if ((ovl || (fused && tails)) && hipEventRecord(aux->rounds[b], s) != hipSuccess) return -1;
                 if (tails) {
                     if (hipStreamWaitEvent(aux->s3, aux->rounds[b], 0) != hipSuccess) return -1;
                     const unsigned lg = (unsigned)std::min<long long>((q.wz_cnt * G + 255) / 256, 512);

@@ -36,6 +36,13 @@ KernelFn prep1(int xf, int rs) {
     if constexpr (RS < 128) return prep1<W, RS + 8>(xf, rs);
     return nullptr;
 }
+// the fused kernel on the same bounds (fused1_kernel_128)
+template <int W, int RS>
+FusedFn fused1(int xf, int rs) {
+    if (rs == RS || RS == 128) return xf ? &k_stack_wz_fused1<128, 1, W, RS> : &k_stack_wz_fused1<128, 0, W, RS>;
+    if constexpr (RS < 128) return fused1<W, RS + 8>(xf, rs);
+    return nullptr;
+}
 template <int NP, int RT, int G, int W, int RS>
 KernelFn straight_rs(int xf, int rs) {
     constexpr int E = NP / G;
@@ -71,6 +78,7 @@ int rs_pick_prep4(int N) {
 }
 
 KernelFn prep1_kernel_128(int xf, int rs) { return prep1<SGPU_WZ_PREP_W128_G1, 72>(xf, rs); }
+FusedFn fused1_kernel_128(int xf, int rs) { return fused1<SGPU_WZ_FUSED_W128, 72>(xf, rs); }
 
 // real-slot bound of the one-lane prep: rs_pick's steps of 8 (N in [rs - 7,
 // rs], which k_stack_wz_prep1's compile-time slot ranges rest on), from 72

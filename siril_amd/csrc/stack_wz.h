@@ -158,7 +158,6 @@ struct RankStore {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #endif
     }
-#if defined(__HIP_DEVICE_COMPILE__)
     // The same store into the HBM record of the prep kernel, with the rank
     // tests moved into buffer descriptors: one raw-buffer descriptor per
     // region (low [0, KT), middle [KT, KT + KM), high [KT + KM, R)), whose
@@ -172,8 +171,12 @@ struct RankStore {
     // regions then hold exactly what store() puts there (plus +Inf in slots of
     // ranks >= kept, which fetch never reads).  Needs NP * stride * 4 <=
     // 2^32 (negative slots >= -NP stay above the record count), which the
-    // launcher enforces (stack_sorted_inst.h).
-    __device__ void store_buf(const float (&v)[E], int g, int kmin, int kmax) {
+    // launcher enforces (stack_sorted_inst.h).  (Host builds, tests/hostsim:
+    // the descriptor's range check restated per store -- drop().)
+    SG_HD void drop(int region0, int size, int slot, float x) {
+        if (slot >= 0 && slot < size) base[(long long)(region0 + slot) * stride + p] = x;
+    }
+    SG_HD void store_buf(const float (&v)[E], int g, int kmin, int kmax) {
         mid0 = kept / 2 - KM / 2;
         hi0 = kept - KT;
         hi0 = hi0 < 0 ? 0 : hi0;
@@ -182,6 +185,7 @@ struct RankStore {
         hi0 = hi0 > eh0 * G ? hi0 : (eh0 > 0 ? eh0 * G : 0);
         mid1 = mid0 + KM < (em1 + 1) * G ? mid0 + KM : (em1 + 1) * G;
         mid0 = mid0 > em0 * G ? mid0 : em0 * G;
+#if defined(__HIP_DEVICE_COMPILE__)
         const uint32_t S4 = (uint32_t)stride * 4u;
         const uint32_t pb = (uint32_t)p * 4u;
         const auto rlo = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)((uint32_t)KT * S4), 0x00020000);
@@ -200,6 +204,14 @@ struct RankStore {
             if (e >= eh0 && e < eln) __builtin_amdgcn_raw_buffer_store_b32(x, rhi, (int)(bhi + eo), 0, 0);
             if (e >= em0 && e <= em1) __builtin_amdgcn_raw_buffer_store_b32(x, rmid, (int)(bmid + eo), 0, 0);
         }
+#else
+        for (int e = 0; e < E; e++) {
+            const int r = e * G + g;
+            if (e < (KT + G - 1) / G) drop(0, KT, r, v[e]);
+            if (e >= eh0 && e < eln) drop(KT + KM, KT, r + KT - kept, v[e]);
+            if (e >= em0 && e <= em1) drop(KT, KM, r - (kept / 2 - KM / 2), v[e]);
+        }
+#endif
     }
     // store_buf for a sorted column in one lane (G = 1, slot = rank) whose
     // wave has kept in [RSL - 7, RSL] in every lane: the slots that can hold
@@ -211,11 +223,12 @@ struct RankStore {
     // store_buf.  Every rank of the three ranges is stored, so hi0 / mid0 /
     // mid1 are the unclipped ones -- what store() leaves for this wave.
     template <int RSL>
-    __device__ void store_full(const float (&v)[E]) {
+    SG_HD void store_full(const float (&v)[E]) {
         static_assert(G == 1 && RSL % 8 == 0 && RSL - 7 - KT >= KT && RSL <= E, "one lane per pixel, N >= 65");
         mid0 = kept / 2 - KM / 2;
         mid1 = mid0 + KM;
         hi0 = kept - KT;
+#if defined(__HIP_DEVICE_COMPILE__)
         const uint32_t S4 = (uint32_t)stride * 4u;
         const uint32_t pb = (uint32_t)p * 4u;
         const auto rlo = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)((uint32_t)KT * S4), 0x00020000);
@@ -234,8 +247,47 @@ struct RankStore {
 #pragma unroll
         for (int e = RSL - 7 - KT; e < RSL; e++)
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[e]), rhi, (int)(bhi + (uint32_t)e * S4), 0, 0);
-    }
+#else
+        for (int e = 0; e < KT; e++) drop(0, KT, e, v[e]);
+        for (int e = RSL / 2 - 4 - KM / 2; e < RSL / 2 + KM / 2; e++) drop(KT, KM, e - mid0, v[e]);
+        for (int e = RSL - 7 - KT; e < RSL; e++) drop(KT + KM, KT, e + KT - kept, v[e]);
 #endif
+    }
+    // store_full into an LDS tile (the fused kernel, k_stack_wz_fused1): LDS
+    // has no descriptor to drop a store, so the order does it.  Same
+    // compile-time slot ranges; a slot below its lane's range lands in the
+    // region underneath (at most 7 slots under the high one: the middle
+    // region; 4 under the middle one: the low region), which is stored
+    // afterwards and whole by every lane (kept >= RSL - 7 >= KT + KM: every
+    // rank of the middle and low regions exists).  Only a slot above the range
+    // needs its test: ranks >= kept (the last 7 slots) and the last 4 middle
+    // slots.  LDS stores of a lane complete in program order.  Leaves the
+    // tile's R slots and hi0 / mid0 / mid1 as store_full leaves the record's.
+    template <int RSL>
+    SG_HD void store_full_lds(const float (&v)[E]) {
+        static_assert(G == 1 && RSL % 8 == 0 && RSL - 7 - KT >= KT && RSL <= E, "one lane per pixel, N >= 65");
+        static_assert(RSL - 7 >= KT + KM && KM / 2 <= KT && 7 <= KM, "a slot under a region stays inside the next one");
+        mid0 = kept / 2 - KM / 2;
+        mid1 = mid0 + KM;
+        hi0 = kept - KT;
+        const int S = (int)stride;
+        float *const bl = base + p;
+        float *const bh = bl + (KT + KM - hi0) * S;      // rank e of the high region at bh[e * S]
+        float *const bm = bl + (KT - mid0) * S;          // of the middle region at bm[e * S]
+#pragma unroll
+        for (int e = RSL - 7 - KT; e < RSL; e++)
+            if (e < RSL - 7 || e < kept) bh[e * S] = v[e];
+#pragma unroll
+        for (int e = RSL / 2 - 4 - KM / 2; e < RSL / 2 + KM / 2; e++)
+            if (e < RSL / 2 || e < mid1) bm[e * S] = v[e];
+#pragma unroll
+        for (int e = 0; e < KT; e++) bl[e * S] = v[e];
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#endif
+    }
     // rank r (0 <= r < kept); false when not stored (the pixel falls back).
     // Branch-free: the slot is selected, one load is issued (slot 0 when the
     // rank is not stored), so the rounds' fetch loops carry no divergent
@@ -955,13 +1007,33 @@ void k_stack_wz_prep(KParams p) {
 // slot loops of the G-lane form in a wave-uniform branch.  Either way the
 // record, the moments (same accumulators, same order) and m.y/z/w are what
 // wz_prepare<128, 1> gives.
-template <int RSL>
-__device__ __forceinline__ void wz_prepare1(float (&v)[128], int kept, int N, RankStore<128, 1> &rs, double &W1,
-                                            double &W2, float &c0) {
-#if defined(__HIP_DEVICE_COMPILE__)   // (store_buf / store_full: device code only)
+// LDS: the ranks go to the wave's LDS tile (k_stack_wz_fused1: rs.base the
+// tile, rs.stride 64, rs.p the lane) through store_full_lds / store instead of
+// the HBM record; everything else is the same code.
+// (wave_any / wave_min: one lane is the wave in a host build, tests/hostsim)
+SG_HD bool wave_any(bool x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __ballot(x) != 0ull;
+#else
+    return x;
+#endif
+}
+SG_HD int wave_min(int x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int lm = 32; lm >= 1; lm >>= 1) x = min(x, __shfl_xor(x, lm, 64));
+    x = __builtin_amdgcn_readfirstlane(x);
+#endif
+    return x;
+}
+// (wz_prepare1_sorted: everything after the sort -- the fused kernel sets its
+// tile's RankStore up between the two, so that nothing of it lives through
+// the sort)
+template <int RSL, bool LDS = false>
+SG_HD void wz_prepare1_sorted(const float (&v)[128], int kept, int N, RankStore<128, 1> &rs, double &W1, double &W2,
+                              float &c0) {
     constexpr int E = 128, K0 = RSL - 7;
     static_assert(RSL % 8 == 0 && RSL >= 72 && RSL <= E, "real-slot buckets of rs_pick(128, 1, N)");
-    sort_col<E, 1, RSL>(v, 0);
     rs.kept = kept;
     const int ra = kept / 2 - ((kept & 1) ? 0 : 1), rb = kept / 2;
     const int el = (N + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1);
@@ -969,8 +1041,9 @@ __device__ __forceinline__ void wz_prepare1(float (&v)[128], int kept, int N, Ra
 #pragma unroll
     for (int q = 0; q < SGPU_NACC; q++) s1[q] = s2[q] = 0.0;
     float sa = 0.f, sb = 0.f;
-    if (__ballot(kept < K0) == 0ull) {
-        rs.store_full<RSL>(v);
+    if (!wave_any(kept < K0)) {
+        if constexpr (LDS) rs.template store_full_lds<RSL>(v);
+        else rs.template store_full<RSL>(v);
 #pragma unroll
         for (int e = RSL / 2 - 4; e <= RSL / 2; e++) {
             sa = (e == ra) ? v[e] : sa;
@@ -987,11 +1060,9 @@ __device__ __forceinline__ void wz_prepare1(float (&v)[128], int kept, int N, Ra
             s2[e % SGPU_NACC] = fma(y, y, s2[e % SGPU_NACC]);
         }
     } else {
-        int kmin = kept;
-#pragma unroll
-        for (int lm = 32; lm >= 1; lm >>= 1) kmin = min(kmin, __shfl_xor(kmin, lm, 64));
-        kmin = __builtin_amdgcn_readfirstlane(kmin);
-        rs.store_buf(v, 0, kmin, N);
+        const int kmin = wave_min(kept);
+        if constexpr (LDS) rs.store(v, 0, kmin, N);
+        else rs.store_buf(v, 0, kmin, N);
         const int ew0 = kmin / 2 - 1, ew1 = N / 2;
 #pragma unroll
         for (int e = 0; e <= RSL / 2; e++) {
@@ -1024,7 +1095,12 @@ __device__ __forceinline__ void wz_prepare1(float (&v)[128], int kept, int N, Ra
         W1 += s1[q];
         W2 += s2[q];
     }
-#endif
+}
+
+template <int RSL, bool LDS = false>
+SG_HD void wz_prepare1(float (&v)[128], int kept, int N, RankStore<128, 1> &rs, double &W1, double &W2, float &c0) {
+    sort_col<128, 1, RSL>(v, 0);
+    wz_prepare1_sorted<RSL, LDS>(v, kept, N, rs, W1, W2, c0);
 }
 
 template <int NP, int XF, int W, int RSL>
@@ -1306,6 +1382,113 @@ __global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p, WzSplit s
             if (is_weighted(p)) res = weighted_mean<U16>(p, pix, (int)(pix % p.W), o.pmin, o.pmax, o.nkept);
             if constexpr (U16) write_result16(p, pix, res, o.rl, o.rh);
             else write_result(p, pix, res, o.rl, o.rh);
+            rl = o.rl;
+            rh = o.rh;
+        }
+    }
+    add_counts(p, rl, rh);
+}
+
+// Fused form (SGPU_WZ=7; float, N = 65..128): k_stack_wz_prep1 and the capped
+// head k_stack_wz_rounds_lds<128, 0, 1> in one kernel, so that the rank record
+// never goes to HBM.  A wave of the one-lane prep holds exactly the 64 pixels
+// of a head block (its tile: wave w of block b is head block 4 b + w), a lane
+// owns its pixel's sorted column, and the R rank slots go straight into the
+// wave's own [slot][lane] LDS tile -- the layout the head stages -- with no
+// cross-wave exchange and no block barrier.  Gather, NaN pin, sort, moments,
+// c0 and meta are wz_prepare1's, the rounds wz_finish_cap's with the same m,
+// the routes the head's; so every pixel ends exactly as on the two-kernel
+// path.  Only a deferring lane leaves something in the workspace, and leaves
+// all k_stack_wz_tail reads: its state, meta, moments, the compact copy of its
+// ranks in its tile of the (otherwise unwritten) record and the list entry.
+// Four waves x 10 KB of LDS per block; the register budget is the prep's
+// (three waves per SIMD), the rounds need fewer once the column is dead.
+template <int NP, int XF, int W, int RSL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
+void k_stack_wz_fused1(KParams p, WzSplit sp) {
+    static_assert(NP == 128, "one lane per pixel: N <= 128");
+    using RS = RankStore<NP, 1>;
+    __shared__ float s_rank[4 * RS::R * 64];
+    // the head block of this wave (wave-uniform; nothing below crosses waves)
+    if (((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 >= p.wz_cnt) return;
+    int kept = 0, bad = 0;
+    double W1, W2;
+    float c0;
+    RS rs;
+    float v[NP];
+    {
+        // a lane past the chunk gathers the wave's first pixel (valid
+        // addresses, wave-uniform code) and is discarded below
+        const long long c = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64, l = c + (threadIdx.x & 63);
+        const long long gp = p.wz_pix0 + (l < p.wz_cnt ? l : c);
+        gather_column<XF, NP, 1, true, 0, RSL, SGPU_GATHER_SLOTSTEP, true>(p, v, gp, (int)(gp % p.W), 0, kept, bad);
+    }
+    opaque(bad);                              // (k_stack_wz_prep1: the NaN test settled before the sort)
+    sort_col<NP, 1, RSL>(v, 0);
+    // everything that depends on the thread index is worked out after the
+    // sort, from a copy of it the compiler cannot trace back: the sort's peak
+    // holds the column, kept and bad, as the prep kernel's does
+    int tid = (int)threadIdx.x;
+    opaque(tid);
+    const int lane = tid & 63;
+    const long long tile = (long long)blockIdx.x * 4 + (tid >> 6);
+    const long long col0 = tile * 64;
+    const long long loc = col0 + lane;
+    const bool live = loc < p.wz_cnt;
+    const long long pix = p.wz_pix0 + (live ? loc : col0);
+    float *const tile_rank = s_rank + (tid >> 6) * (RS::R * 64);
+    rs.base = tile_rank;
+    rs.stride = 64;
+    rs.p = lane;
+    wz_prepare1_sorted<RSL, true>(v, kept, p.nframes, rs, W1, W2, c0);
+    int rl = 0, rh = 0;
+    if (live) {
+        int route = 2;
+        PixOut o;
+        WzState st;
+        if (!bad && kept > 0) {
+            const int N = p.nframes;
+            const int el = (N + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1);   // the prep's slots (G = 1)
+            route = wz_finish_cap<0>(rs, kept, W1, W2, c0, el, p.sig0, p.sig1, sp.cap, o, st);
+        }
+        if (route == kWzDeferred) {
+            // as the head: state, compact copy of the ranks, striped list
+            // entry -- and what the prep kernel would have left for the tail
+            const unsigned long long dm = __ballot(true);
+            const int ci = (int)__popcll(dm & ((1ull << lane) - 1ull));
+            const int tw = (int)(p.wz_cnt - col0 < 64 ? p.wz_cnt - col0 : 64);
+            const int stripe = (int)tile / sp.bps;
+            const int slot = wave_append(sp.cnt_out + stripe * kWzStripeStep, true);
+            sp.list_out[stripe * sp.bps * 64 + slot] = wz_entry((int)tile, ci, lane);
+            reinterpret_cast<WzState *>(p.wz_state)[loc] = st;
+            p.wz_mom[loc] = W1;
+            p.wz_mom[p.wz_cnt + loc] = W2;
+            p.wz_mom[2 * p.wz_cnt + loc] = (double)c0;
+            reinterpret_cast<int4 *>(p.wz_meta)[loc] = make_int4(kept, rs.hi0, rs.mid0, rs.mid1);
+            if (tw == 64 && (p.wz_cnt & 3) == 0) {
+                const unsigned cnt = (unsigned)p.wz_cnt, c0w = (unsigned)col0;
+#pragma unroll 2
+                for (int j = 0; j < RS::R; j += 4) {
+                    const unsigned f = (unsigned)(ci * RS::R + j);
+                    const float4 q = make_float4(tile_rank[j * 64 + lane], tile_rank[(j + 1) * 64 + lane],
+                                                 tile_rank[(j + 2) * 64 + lane], tile_rank[(j + 3) * 64 + lane]);
+                    *reinterpret_cast<float4 *>(p.wz_ranks + (umul24(f >> 6, cnt) + c0w + (f & 63u))) = q;
+                }
+            } else {
+#pragma unroll 4
+                for (int j = 0; j < RS::R; j++)
+                    p.wz_ranks[wz_crec_index(ci * RS::R + j, tw, p.wz_cnt, col0)] = tile_rank[j * 64 + lane];
+            }
+        } else if (route == 1) {
+            const int slot = wave_append(p.fb2_count, true);
+            p.fb2_list[slot] = (int)pix;
+        } else if (route == 2) {
+            const int slot = wave_append(p.fb_count, true);
+            p.fb_list[slot] = (int)pix;
+        } else {
+            double res = o.res;
+            if (is_weighted(p)) res = weighted_mean<0>(p, pix, (int)(pix % p.W), o.pmin, o.pmax, o.nkept);
+            write_result(p, pix, res, o.rl, o.rh);
             rl = o.rl;
             rh = o.rh;
         }

@@ -206,6 +206,11 @@ class Context:
     def last_exact_pixels(self) -> int:
         return int(lib().sgpu_last_exact_pixels(self.h))
 
+    def last_wz_fallback(self) -> int:
+        """Pixels the last WINSORIZED stack's moment path handed to the sorted
+        kernel (sgpu_last_wz_fallback)."""
+        return int(lib().sgpu_last_wz_fallback(self.h))
+
     def last_wz_deferred(self):
         """(pixels into tail pass 1, into tail pass 2) of the last float WINSORIZED
         stack's split rounds (sgpu_last_wz_deferred); (0, 0) when the split did not run."""
