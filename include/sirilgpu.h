@@ -617,6 +617,47 @@ int sgpu_calibrate_frames_device(sgpu_context *ctx, const void *d_in, float *d_o
 		const float *d_dark, const float *d_flat, float norm, float *d_k, const int *d_list, long count,
 		int cfa, int dark_optim);
 
+/* ---- background extraction (the `seqsubsky <seq> <degree>` command) -------- */
+
+/* Arithmetic: the specification in DESIGN.md 6i (B0-B7), restated in
+ * tests/bkg_ref.py; parity with a Siril binary is unpinned.  A plane is
+ * width x height samples (elem_size 2: WORD, scaled by 1/65535; 4: float);
+ * every plane is treated on its own: medians of a grid of 25 x 25 sample
+ * boxes, selection of the sky boxes, a least-squares polynomial of the given
+ * degree through them, subtraction of (or division by) the polynomial with
+ * its mean put back. */
+typedef struct {
+	int degree;          /* 1 .. 4 */
+	int samples;         /* boxes per line; the box spacing is width / samples */
+	double tolerance;    /* a box is kept when 0 < median <= m + tolerance * MAD; >= 0 */
+	int divide;          /* 0: subtract, else divide */
+} sgpu_bkg_params;
+#define SGPU_BKG_NCOEF 15   /* coefficients of u^i v^j by total degree, then by j; unused ones are 0 */
+#define SGPU_BKG_MAX_BOXES 8192
+/* degree 1, samples 20, tolerance 1.0, subtraction */
+void sgpu_bkg_default_params(sgpu_bkg_params *params);
+/* The sample grid of a width x height plane (host only): nx * ny boxes, box
+ * (i, j) centred at (12 + startx + i*dist, 12 + starty + j*dist).  A plane
+ * smaller than one box, samples < 1, samples > width and more than
+ * SGPU_BKG_MAX_BOXES boxes return SGPU_BAD_ARGUMENT.  Outputs are optional. */
+int sgpu_bkg_grid(int width, int height, int samples, int *nx, int *ny, int *dist, int *startx, int *starty);
+/* nplanes planes (plane p at d_in + p*plane_stride samples, the output at
+ * d_out + p*plane_stride floats) in three launches on the context's stream;
+ * asynchronous, nothing is copied to the host.  Results per plane, in device
+ * memory: d_med[nplanes * K] box medians, d_keep[nplanes * K] 1 for a kept box,
+ * d_coef[nplanes * 15], d_mean (the mean of the model over the plane), d_kept,
+ * d_status: 0, 1 (fewer kept boxes than coefficients) or 2 (the normal matrix
+ * is not positive definite).  A plane whose status is not 0 is written as its
+ * converted input.  A result array may be null; it then lives in the context
+ * until the next call.  d_out may be d_in only for float input.  nplanes == 0
+ * does nothing.  Bad sizes, parameters or grids return SGPU_BAD_ARGUMENT. */
+int sgpu_subsky_planes_device(sgpu_context *ctx, const void *d_in, int elem_size, int nplanes, int width, int height,
+		long plane_stride, const sgpu_bkg_params *params, float *d_out, float *d_med, unsigned char *d_keep,
+		double *d_coef, double *d_mean, int *d_kept, int *d_status);
+/* Kernel times of the last sgpu_subsky_planes_device call (HIP events on the
+ * context's stream; waits for the call): box medians, fit, streaming pass. */
+int sgpu_bkg_last_kernel_ms(sgpu_context *ctx, float ms[3]);
+
 /* ---- star detection and star-based global registration ------------------- */
 
 /* Arithmetic: the specification in DESIGN.md 6f, restated in

@@ -49,6 +49,8 @@ EXPORTS = (
     "sgpu_drizzle_frames_device", "sgpu_drizzle_last_tiles",
     "sgpu_region_stats_device", "sgpu_equalize_cfa_flat_device", "sgpu_find_deviant_pixels_device",
     "sgpu_cosmetic_correction_device", "sgpu_dark_optimize_device", "sgpu_calibrate_frames_device",
+    "sgpu_bkg_default_params", "sgpu_bkg_grid", "sgpu_subsky_planes_device",
+    "sgpu_bkg_last_kernel_ms",
     "sgpu_star_default_params", "sgpu_match_default_params", "sgpu_star_smooth_table", "sgpu_find_stars_device",
     "sgpu_star_last_candidates", "sgpu_star_last_kernel_ms", "sgpu_match_stars",
     "sgpu_psf_default_params", "sgpu_fit_stars_device", "sgpu_psf_last_kernel_ms",
@@ -102,6 +104,11 @@ class PsfParams(C.Structure):
 class DrizzleParams(C.Structure):
     """sgpu_drizzle_params (include/sirilgpu.h)."""
     _fields_ = [("scale", C.c_double), ("pixfrac", C.c_double), ("kernel", C.c_int), ("reserved", C.c_int)]
+
+
+class BkgParams(C.Structure):
+    """sgpu_bkg_params (include/sirilgpu.h)."""
+    _fields_ = [("degree", C.c_int), ("samples", C.c_int), ("tolerance", C.c_double), ("divide", C.c_int)]
 
 
 class MatchParams(C.Structure):
@@ -378,6 +385,15 @@ def lib():
         L.sgpu_calibrate_frames_device.restype = i
         L.sgpu_calibrate_frames_device.argtypes = [vp, vp, vp, i, i, i, i, C.c_long, vp, i, f, vp, vp, f, vp, vp,
                                                    C.c_long, i, i]
+        L.sgpu_bkg_default_params.restype = None
+        L.sgpu_bkg_default_params.argtypes = [C.POINTER(BkgParams)]
+        L.sgpu_bkg_grid.restype = i
+        L.sgpu_bkg_grid.argtypes = [i, i, i, pi, pi, pi, pi, pi]
+        L.sgpu_subsky_planes_device.restype = i
+        L.sgpu_subsky_planes_device.argtypes = [vp, vp, i, i, i, i, C.c_long, C.POINTER(BkgParams), vp, vp, vp, vp, vp,
+                                                vp, vp]
+        L.sgpu_bkg_last_kernel_ms.restype = i
+        L.sgpu_bkg_last_kernel_ms.argtypes = [vp, C.POINTER(f)]
         L.sgpu_star_default_params.restype = None
         L.sgpu_star_default_params.argtypes = [C.POINTER(StarParams)]
         L.sgpu_match_default_params.restype = None

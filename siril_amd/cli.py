@@ -15,7 +15,12 @@ the warped 32-bit <prefix><name>NNNNN.fit and their .seq.  -psf=gaussian|moffat 
 homographies `register -noout` wrote, as `register`'s output stage does; `seqapplyreg <seq> -drizzle [-scale=1]
 [-pixfrac=1] [-kernel=point|turbo|square] [-flat=FILE] [-layer=N] [-prefix=r_]` drizzles the frames instead: 32-bit
 <prefix><name>NNNNN.fit of the scaled size, their weight planes in drizztmp/oweight_<prefix><name>NNNNN.fit, and a
-.seq with the drizzle flag set."""
+.seq with the drizzle flag set.
+
+`python -m siril_amd.cli seqsubsky <seq> <degree> [-samples=20] [-tolerance=1.0] [-nodither] [-prefix=bkg_]`: polynomial
+background extraction of every frame (siril_amd/background.py), degree 1 .. 4, each layer on its own; writes 32-bit
+<prefix><name>NNNNN.fit and the new .seq.  -nodither is accepted (the output is float, nothing is dithered); -rbf and
+-smooth= are refused."""
 import sys
 import time
 
@@ -28,6 +33,13 @@ def main(argv=None):
         out, k = run_calibrate(argv)
         print(f"Calibrated to {out} in {time.perf_counter() - t0:.3f} s" +
               ("" if k is None else "; dark factors " + " ".join(f"{v:.4f}" for v in k)))
+        return 0
+    if argv and argv[0] == "seqsubsky":
+        from siril_amd.background import run_seqsubsky
+        t0 = time.perf_counter()
+        out, info = run_seqsubsky(argv)
+        print(f"Background extracted to {out} in {time.perf_counter() - t0:.3f} s; sample boxes kept per plane "
+              f"{int(info['kept'].min())} .. {int(info['kept'].max())}")
         return 0
     if argv and argv[0] == "register":
         from siril_amd.registration import run_register

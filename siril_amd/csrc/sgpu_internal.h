@@ -151,6 +151,12 @@ struct sgpu_context {
     sgpu_host::DevBuf psf_jobs, psf_out;
     hipEvent_t psf_ev[2] = {nullptr, nullptr};             // fit kernel start, stop
     float psf_ms = 0.f;                                    // last call: fit kernel time
+    // background extraction: the result arrays a caller did not pass
+    sgpu_host::DevBuf bkg_ws, bkg_mom;                     // ... and the axis moments of the last plane size
+    hipEvent_t bkg_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // box medians start, fit start, apply start, stop
+    double bkg_M[10] = {};                                 // axis moments Mx[0 .. 4], My[0 .. 4] of bkg_M_key's size
+    int bkg_M_key[2] = {0, 0};
+    int bkg_timed = 0;                                     // the events of a call are recorded
 
     void release_all() {
         for (sgpu_host::DevBuf *b : {&fb_list, &fb_count, &counts, &scratch, &scale, &offset, &mul,
@@ -159,7 +165,7 @@ struct sgpu_context {
                                      &dft_frames, &rl_u, &rl_e, &rl_f, &rl_r, &rl_w, &rl_taps, &rl_small,
                                      &rl_io, &rl_reg, &rl_gxy, &rlf_t1, &rlf_t2, &rlf_ka, &rlf_kb, &rlf_kt, &rlf_tw1, &rlf_tw2, &dm_ws, &dm_mm, &dm_io, &ns_state, &ns_hist, &ns_part, &ns_io, &bn_rows, &qe_buf, &qe_part, &qe_io, &onorm, &ov_ws, &ov_tab,
                                      &fb2_list, &fb2_count, &wz_ws, &wz_cnt, &fe_tab, &fe_dt, &cfa_tmp, &cstripe, &warp_ws, &drz_ws, &cal_rows, &cal_k, &cal_cnt, &cal_plan,
-                                     &star_tc, &star_slots, &star_fp, &star_out, &psf_jobs, &psf_out,
+                                     &star_tc, &star_slots, &star_fp, &star_out, &psf_jobs, &psf_out, &bkg_ws, &bkg_mom,
                                      &seq_in[0], &seq_in[1], &seq_out, &seq_lo, &seq_hi, &seq_cnt})
             b->release();
         seq_pin[0].release();
