@@ -558,9 +558,26 @@ int sgpu_drizzle_check_maps(int nframes, const double *A, int width, int height,
 int sgpu_drizzle_frames_device(sgpu_context *ctx, const void *d_in, int elem_size, int nframes, int width,
 		int height, long frame_stride, const float *d_pixel_weights, const double *H, int ref_index,
 		const sgpu_drizzle_params *params, float *d_out, float *d_out_weights, long out_frame_stride);
-/* Output tiles of the last sgpu_drizzle_frames_device call that read drops
- * staged in LDS (counts[0]) and that mapped every candidate themselves
- * (counts[1]). */
+/* sgpu_drizzle_frames_device of colour-filter-array frames (seqapplyreg
+ * -drizzle -cfa=): every input pixel lands in the plane of its own colour
+ * only.  pattern (host memory): pattern_dim * pattern_dim bytes, 0 R, 1 G,
+ * 2 B, pattern_dim 2 (Bayer) or 6 (X-Trans); memory-order input pixel (i, j)
+ * has colour pattern[(j % dim) * dim + i % dim].  Per frame three float
+ * images and three float weight planes: channel c of frame f lies at
+ * f * out_frame_stride + c * out_plane_stride floats, out_plane_stride >=
+ * out_w * out_h, out_frame_stride >= 3 * out_plane_stride; a colour that is
+ * not in the pattern gives an all-zero channel of zero weights.  Channel c
+ * equals sgpu_drizzle_frames_device with the pixel weights w * [colour == c]
+ * (w: d_pixel_weights, or 1) bit for bit.  Other arguments and refusals as
+ * sgpu_drizzle_frames_device; a pattern entry above 2 or another pattern_dim
+ * returns SGPU_BAD_ARGUMENT.  Synchronous. */
+int sgpu_drizzle_cfa_frames_device(sgpu_context *ctx, const void *d_in, int elem_size, int nframes, int width,
+		int height, long frame_stride, const float *d_pixel_weights, const unsigned char *pattern,
+		int pattern_dim, const double *H, int ref_index, const sgpu_drizzle_params *params, float *d_out,
+		float *d_out_weights, long out_plane_stride, long out_frame_stride);
+/* Output tiles of the last sgpu_drizzle_frames_device or
+ * sgpu_drizzle_cfa_frames_device call that read drops staged in LDS
+ * (counts[0]) and that mapped every candidate themselves (counts[1]). */
 int sgpu_drizzle_last_tiles(sgpu_context *ctx, long counts[2]);
 
 /* ---- calibration (the `calibrate` command: preprocess()) ------------------ */
@@ -910,8 +927,11 @@ int sgpu_last_timing(sgpu_context *ctx, float ms[2]);
  * A regular FITS sequence whose drizzle_flag is set (seqapplyreg -drizzle):
  * a mean stack reads the rows of drizztmp/oweight_<frame file> beside every
  * frame with each block and stacks with them as the drizzle weights of
- * sgpu_stack_rows_planes_device; a missing weight file, or registration
- * shifts / -maximize on such a sequence, return SGPU_SEQUENCE_ERROR.
+ * sgpu_stack_rows_planes_device; a weight file of as many layers as the
+ * frames (seqapplyreg -drizzle -cfa=) gives layer l its own layer l, a
+ * one-layer file serves every layer; a missing weight file, one of any other
+ * layer count, or registration shifts / -maximize on such a sequence, return
+ * SGPU_SEQUENCE_ERROR.
  * Returns ST_*. */
 int sgpu_stack_seq(sgpu_context *ctx, const char *seq_path, const sgpu_stack_params *params,
 		int use_registration, int use_32bit_output, const char *out_path, uint64_t counts[2],

@@ -46,7 +46,7 @@ EXPORTS = (
     "sgpu_feather_block_device", "sgpu_set_seq_readers", "sgpu_last_seq_stats", "sgpu_release_seq_buffers",
     "sgpu_warp_frames_device", "sgpu_warp_inverse_maps", "sgpu_warp_table", "sgpu_warp_last_tiles",
     "sgpu_drizzle_output_size", "sgpu_drizzle_forward_maps", "sgpu_drizzle_check_maps",
-    "sgpu_drizzle_frames_device", "sgpu_drizzle_last_tiles",
+    "sgpu_drizzle_frames_device", "sgpu_drizzle_cfa_frames_device", "sgpu_drizzle_last_tiles",
     "sgpu_region_stats_device", "sgpu_equalize_cfa_flat_device", "sgpu_find_deviant_pixels_device",
     "sgpu_cosmetic_correction_device", "sgpu_dark_optimize_device", "sgpu_calibrate_frames_device",
     "sgpu_bkg_default_params", "sgpu_bkg_grid", "sgpu_subsky_planes_device",
@@ -369,6 +369,9 @@ def lib():
         L.sgpu_drizzle_frames_device.restype = i
         L.sgpu_drizzle_frames_device.argtypes = [vp, vp, i, i, i, i, C.c_long, vp, vp, i, C.POINTER(DrizzleParams),
                                                  vp, vp, C.c_long]
+        L.sgpu_drizzle_cfa_frames_device.restype = i
+        L.sgpu_drizzle_cfa_frames_device.argtypes = [vp, vp, i, i, i, i, C.c_long, vp, vp, i, vp, i,
+                                                     C.POINTER(DrizzleParams), vp, vp, C.c_long, C.c_long]
         L.sgpu_drizzle_last_tiles.restype = i
         L.sgpu_drizzle_last_tiles.argtypes = [vp, C.POINTER(C.c_long)]
         pl, pd = C.POINTER(C.c_long), C.POINTER(C.c_double)

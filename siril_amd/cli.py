@@ -10,12 +10,15 @@ siril_amd/sequence.py).  Prints the output path and the rejection totals.
 [-maxstars=N] [-noout] [-interp=ne|li|cu|ar|la] [-noclamp] [-prefix=r_] [-psf=moments|gaussian|moffat]`: star-based
 global registration (siril_amd/registration.py); rewrites the .seq with the homographies and, unless -noout, writes
 the warped 32-bit <prefix><name>NNNNN.fit and their .seq.  -psf=gaussian|moffat measures the stars with a PSF fit.
+`register <seq> -cfa=RGGB|BGGR|GBRG|GRBG|<36 letters> -noout` registers colour-filter-array mosaics: the stars are
+looked for on a copy of every frame with its non-green pixels interpolated.
 
 `python -m siril_amd.cli seqapplyreg <seq> [-layer=N] [-prefix=r_] [-interp=ne|li|cu|ar|la] [-noclamp]` applies the
 homographies `register -noout` wrote, as `register`'s output stage does; `seqapplyreg <seq> -drizzle [-scale=1]
 [-pixfrac=1] [-kernel=point|turbo|square] [-flat=FILE] [-layer=N] [-prefix=r_]` drizzles the frames instead: 32-bit
 <prefix><name>NNNNN.fit of the scaled size, their weight planes in drizztmp/oweight_<prefix><name>NNNNN.fit, and a
-.seq with the drizzle flag set.
+.seq with the drizzle flag set.  With -cfa=RGGB|BGGR|GBRG|GRBG|<36 letters> the frames are mosaics of that pattern:
+every input pixel lands in the plane of its own colour, and the frames, the weight files and the .seq have three layers.
 
 `python -m siril_amd.cli seqsubsky <seq> <degree> [-samples=20] [-tolerance=1.0] [-nodither] [-prefix=bkg_]`: polynomial
 background extraction of every frame (siril_amd/background.py), degree 1 .. 4, each layer on its own; writes 32-bit

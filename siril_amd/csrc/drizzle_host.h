@@ -268,7 +268,61 @@ SGPU_DRZ_HD inline void drz_gather_pixel(const T *in, const float *pw, int W, co
         }
 }
 
+// ---- CFA frames: one (out, vc) pair per colour, an input pixel updates its own colour's only ----
+
+// colour (0 R, 1 G, 2 B) of memory-order input pixel (i, j); pattern holds dim * dim entries
+SGPU_DRZ_HD inline int drz_cfa_colour(const unsigned char *pattern, int dim, int i, int j) {
+    return pattern[(j % dim) * dim + (i % dim)];
+}
+
+// drz_update on the pair of colour c.  The pair is selected in and out: c is a run-time value and
+// must not index registers.
+SGPU_DRZ_HD inline void drz_update_cfa(float &o0, float &v0, float &o1, float &v1, float &o2, float &v2, int c,
+                                       float d, float dow) {
+    float o = c == 0 ? o0 : (c == 1 ? o1 : o2), v = c == 0 ? v0 : (c == 1 ? v1 : v2);
+    drz_update(o, v, d, dow);
+    o0 = c == 0 ? o : o0;
+    v0 = c == 0 ? v : v0;
+    o1 = c == 1 ? o : o1;
+    v1 = c == 1 ? v : v1;
+    o2 = c == 2 ? o : o2;
+    v2 = c == 2 ? v : v2;
+}
+
+// drz_gather_pixel of a CFA frame: out[c], vc[c] of the three colours
+template <typename T>
+SGPU_DRZ_HD inline void drz_gather_pixel_cfa(const T *in, const float *pw, const unsigned char *pattern, int dim,
+                                             int W, const double *A, double scale, double pixfrac, int kernel,
+                                             int i0, int i1, int j0, int j1, int X, int Y, float out[3],
+                                             float vc[3]) {
+    float o0 = 0.f, v0 = 0.f, o1 = 0.f, v1 = 0.f, o2 = 0.f, v2 = 0.f;
+    for (int j = j0; j <= j1; j++)
+        for (int i = i0; i <= i1; i++) {
+            const float w = pw ? pw[(long long)j * W + i] : 1.f;
+            if (w == 0.f) continue;
+            const float dow = drz_dow_pixel(A, scale, pixfrac, kernel, i, j, (double)X, (double)Y, w);
+            if (dow > 0.f)
+                drz_update_cfa(o0, v0, o1, v1, o2, v2, drz_cfa_colour(pattern, dim, i, j),
+                               drz_sample(in[(long long)j * W + i]), dow);
+        }
+    out[0] = o0;
+    out[1] = o1;
+    out[2] = o2;
+    vc[0] = v0;
+    vc[1] = v1;
+    vc[2] = v2;
+}
+
 // ---- host side: checks, size rule, maps, refusals ----
+
+// nullptr when the pattern is a Bayer (dim 2) or X-Trans (dim 6) one of entries 0 .. 2, else what is wrong
+inline const char *drz_check_pattern(const unsigned char *pattern, int dim) {
+    if (!pattern) return "drizzle: no CFA pattern";
+    if (dim != 2 && dim != 6) return "drizzle: the CFA pattern is 2 x 2 (Bayer) or 6 x 6 (X-Trans)";
+    for (int k = 0; k < dim * dim; k++)
+        if (pattern[k] > 2) return "drizzle: CFA pattern entries are 0 (R), 1 (G) or 2 (B)";
+    return nullptr;
+}
 
 // nullptr when the parameters are in range, else what is wrong
 inline const char *drz_check_params(const sgpu_drizzle_params *p) {
@@ -419,6 +473,71 @@ inline void drz_gather_frame(const T *in, const float *pw, int W, int H, const d
                 drz_window_clip(u0, u1, v0, v1, 0, W - 1, 0, H - 1, i0, i1, j0, j1);
             drz_gather_pixel(in, pw, W, A, p->scale, p->pixfrac, p->kernel, i0, i1, j0, j1, X, Y,
                              out[(size_t)Y * OW + X], vc[(size_t)Y * OW + X]);
+        }
+}
+
+// drz_scatter_frame of a CFA frame: planes out[c * plane + Y * OW + X], plane >= OW * OH, of the
+// three colours; the pixel of colour c updates plane c only
+template <typename T>
+SGPU_DRZ_HD inline void drz_scatter_frame_cfa(const T *in, const float *pw, const unsigned char *pattern, int dim,
+                                              int W, int H, const double *A, const sgpu_drizzle_params *p, int OW,
+                                              int OH, size_t plane, float *out, float *vc) {
+    for (int c = 0; c < 3; c++)
+        for (size_t k = 0; k < (size_t)OW * (size_t)OH; k++) out[c * plane + k] = vc[c * plane + k] = 0.f;
+    const double r = 0.5 * p->pixfrac * p->scale;
+    for (int j = 0; j < H; j++)
+        for (int i = 0; i < W; i++) {
+            const float w = pw ? pw[(size_t)j * W + i] : 1.f;
+            if (w == 0.f) continue;
+            const float d = drz_sample(in[(size_t)j * W + i]);
+            const size_t base = (size_t)drz_cfa_colour(pattern, dim, i, j) * plane;
+            double x0, x1, y0, y1;
+            DrzQuad q;
+            double xo = 0.0, yo = 0.0;
+            if (p->kernel == SGPU_DRIZZLE_SQUARE) {
+                if (!drz_quad(A, p->scale, p->pixfrac, i, j, q)) continue;
+                drz_quad_bounds(q, x0, x1, y0, y1);
+            } else {
+                drz_map(A, p->scale, (double)i, (double)j, xo, yo);
+                if (!drz_finite(xo) || !drz_finite(yo)) continue;
+                if (p->kernel == SGPU_DRIZZLE_TURBO) drz_turbo_bounds(xo, yo, r, x0, x1, y0, y1);
+                else {
+                    x0 = x1 = floor(xo + 0.5);
+                    y0 = y1 = floor(yo + 0.5);
+                }
+            }
+            const int X0 = drz_clip(x0, 0, OW), X1 = drz_clip(x1, -1, OW - 1);
+            const int Y0 = drz_clip(y0, 0, OH), Y1 = drz_clip(y1, -1, OH - 1);
+            for (int Y = Y0; Y <= Y1; Y++)
+                for (int X = X0; X <= X1; X++) {
+                    float dow;
+                    if (p->kernel == SGPU_DRIZZLE_SQUARE) dow = drz_dow_square(q, (double)X, (double)Y, w);
+                    else if (p->kernel == SGPU_DRIZZLE_TURBO) dow = drz_dow_turbo(xo, yo, r, (double)X, (double)Y, w);
+                    else dow = w;
+                    if (dow > 0.f) drz_update(out[base + (size_t)Y * OW + X], vc[base + (size_t)Y * OW + X], d, dow);
+                }
+        }
+}
+
+// drz_gather_frame of a CFA frame, planes as drz_scatter_frame_cfa lays them out
+template <typename T>
+inline void drz_gather_frame_cfa(const T *in, const float *pw, const unsigned char *pattern, int dim, int W, int H,
+                                 const double *A, const double *M, const sgpu_drizzle_params *p, int OW, int OH,
+                                 size_t plane, float *out, float *vc) {
+    const double g = drz_grow(p->kernel, p->scale, p->pixfrac), wd = drz_widen(p->kernel, p->pixfrac);
+    for (int Y = 0; Y < OH; Y++)
+        for (int X = 0; X < OW; X++) {
+            double u0, u1, v0, v1;
+            int i0 = 0, i1 = W - 1, j0 = 0, j1 = H - 1;   // an irregular window: every pixel is a candidate
+            if (drz_window(M, p->scale, X - 0.5 - g, X + 0.5 + g, Y - 0.5 - g, Y + 0.5 + g, wd, u0, u1, v0, v1))
+                drz_window_clip(u0, u1, v0, v1, 0, W - 1, 0, H - 1, i0, i1, j0, j1);
+            float o[3], v[3];
+            drz_gather_pixel_cfa(in, pw, pattern, dim, W, A, p->scale, p->pixfrac, p->kernel, i0, i1, j0, j1, X, Y, o,
+                                 v);
+            for (int c = 0; c < 3; c++) {
+                out[c * plane + (size_t)Y * OW + X] = o[c];
+                vc[c * plane + (size_t)Y * OW + X] = v[c];
+            }
         }
 }
 

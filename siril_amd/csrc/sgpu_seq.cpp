@@ -1570,6 +1570,9 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
             if (int r = fits_open(wp.c_str(), wfr[k])) return r;
             if (wfr[k].w != Win || wfr[k].h != Hin || wfr[k].file_bitpix != -32)
                 return fail(SGPU_SEQUENCE_ERROR, "drizzle weight file is not a 32-bit plane of the frames' size: " + wp);
+            // one plane serves every layer; a plane per layer (seqapplyreg -drizzle -cfa=) is read layer by layer
+            if (wfr[k].nlayers != 1 && wfr[k].nlayers != NL)
+                return fail(SGPU_SEQUENCE_ERROR, "drizzle weight file has neither one layer nor the frames' layers: " + wp);
         }
     }
     // both kinds of weight planes stack from device-resident blocks
@@ -1664,7 +1667,8 @@ int stack_seq_impl(sgpu_context *ctx, const char *seq_path, const sgpu_stack_par
                     if (!errs[t]) place_rows(rows_in.data(), Win, dst, W, nr, shiftx[k], es);
                 }
                 if (drizzled && !errs[t])
-                    errs[t] = read_rows(wfr[k], 0, r0, nr, hbw[slot].data() + (size_t)k * nr * W, tmp, READ_RAW);
+                    errs[t] = read_rows(wfr[k], wfr[k].nlayers == 1 ? 0 : layer, r0, nr,
+                                        hbw[slot].data() + (size_t)k * nr * W, tmp, READ_RAW);
             }
         };
         std::vector<std::thread> pool;

@@ -386,7 +386,7 @@ def drizzle_last_tiles(ctx) -> tuple:
 
 
 def drizzle_frames(frames, Hs, ref_index: int, scale: float = 1.0, pixfrac: float = 1.0, kernel="square",
-                   pixel_weights=None, out=None, out_weights=None, ctx=None):
+                   pixel_weights=None, out=None, out_weights=None, ctx=None, cfa=None):
     """Drizzle frames [N, H, W] (CUDA tensor, float32 or 16-bit WORD storage
     taken as (float)v) through Href^-1 * Hf onto the reference grid scaled by
     `scale` (0.1 .. 4), each input pixel shrunk to `pixfrac` (0 < pixfrac <= 1)
@@ -395,7 +395,13 @@ def drizzle_frames(frames, Hs, ref_index: int, scale: float = 1.0, pixfrac: floa
     the pixel), or None.  Returns (image, weights): float32 [N, out_h, out_w]
     each, fully overwritten; a pixel nothing landed on is 0 with weight 0, and
     `weights` is what Context.stack(drizzle=) takes.  The arithmetic is the
-    specification in DESIGN.md "Drizzle" (Siril parity unpinned)."""
+    specification in DESIGN.md "Drizzle" (Siril parity unpinned).
+    cfa: the frames are colour-filter-array mosaics of this pattern (a 4- or
+    36-letter string, or its compiled bytes, indexed in memory order like
+    interpolate_nongreen's).  Every input pixel then lands in the plane of its
+    own colour only, and image and weights are [N, 3, out_h, out_w] (R, G, B):
+    channel c is, bit for bit, the drizzle with the pixel weights
+    pixel_weights * [colour == c]; a colour the pattern lacks gives zeros."""
     import torch
     from .stacking import Context
     ctx = ctx or Context(frames.device.index or 0)
@@ -407,21 +413,30 @@ def drizzle_frames(frames, Hs, ref_index: int, scale: float = 1.0, pixfrac: floa
     H = np.ascontiguousarray(np.asarray(Hs, np.float64).reshape(n, 9))
     p = _drizzle_params(scale, pixfrac, kernel)
     ow, oh = drizzle_output_size(w, h, p.scale)
+    pat, dim = _cfa_args(cfa)
     pwp = None
     if pixel_weights is not None:
         if (not pixel_weights.is_cuda or pixel_weights.dtype != torch.float32 or tuple(pixel_weights.shape) != (h, w)
                 or not pixel_weights.is_contiguous() or pixel_weights.device != frames.device):
             raise ValueError("pixel_weights must be a contiguous float32 CUDA tensor [H, W] on the frames' device")
         pwp = C.c_void_p(pixel_weights.data_ptr())
+    shape = (n, oh, ow) if pat is None else (n, 3, oh, ow)
     planes = []
     for t, name in ((out, "out"), (out_weights, "out_weights")):
         if t is None:
-            t = torch.empty((n, oh, ow), dtype=torch.float32, device=frames.device)
-        if (tuple(t.shape) != (n, oh, ow) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+            t = torch.empty(shape, dtype=torch.float32, device=frames.device)
+        if (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
                 or t.device != frames.device):
-            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor [{n}, {oh}, {ow}]")
+            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor {list(shape)}")
         planes.append(t)
     ctx.set_stream(torch.cuda.current_stream(frames.device).cuda_stream)
+    if pat is not None:
+        check(lib().sgpu_drizzle_cfa_frames_device(ctx.h, C.c_void_p(frames.data_ptr()), frames.element_size(), n, w, h,
+                                                   h * w, pwp, pat.ctypes.data_as(C.c_void_p), dim,
+                                                   H.ctypes.data_as(C.c_void_p), int(ref_index), C.byref(p),
+                                                   C.c_void_p(planes[0].data_ptr()), C.c_void_p(planes[1].data_ptr()),
+                                                   oh * ow, 3 * oh * ow), "sgpu_drizzle_cfa_frames_device")
+        return planes[0], planes[1]
     check(lib().sgpu_drizzle_frames_device(ctx.h, C.c_void_p(frames.data_ptr()), frames.element_size(), n, w, h, h * w,
                                            pwp, H.ctypes.data_as(C.c_void_p), int(ref_index), C.byref(p),
                                            C.c_void_p(planes[0].data_ptr()), C.c_void_p(planes[1].data_ptr()),
@@ -739,6 +754,15 @@ INTERPOLATIONS = {"nearest": OPENCV_NEAREST, "ne": OPENCV_NEAREST, "linear": OPE
                   "lanczos4": OPENCV_LANCZOS4, "la": OPENCV_LANCZOS4}
 
 
+def _parse_cfa_option(value: str) -> str:
+    """The pattern of a -cfa= option: one of the four Bayer strings, or the 36
+    letters (R, G, B) of an X-Trans pattern."""
+    v = value.upper()
+    if v not in BAYER_PATTERNS and not (len(v) == 36 and set(v) <= set("RGB")):
+        raise ValueError(f"Unknown CFA pattern {value}: RGGB, BGGR, GBRG, GRBG or 36 letters of R, G, B")
+    return v
+
+
 class RegisterCommand:
     def __init__(self, seq: str):
         self.seq = seq
@@ -751,12 +775,15 @@ class RegisterCommand:
         self.clamp = True
         self.prefix = "r_"
         self.psf = "moments"
+        self.cfa = None
 
 
 def parse_register_command(words) -> RegisterCommand:
     """`register <seq> [-layer=] [-transf=shift|similarity|affine|homography]
     [-minpairs=] [-maxstars=] [-noout] [-interp=ne|li|cu|ar|la] [-noclamp]
-    [-prefix=r_] [-psf=moments|gaussian|moffat]`."""
+    [-prefix=r_] [-psf=moments|gaussian|moffat] [-cfa=PATTERN -noout]`.
+    -cfa= (the frames are mosaics of that pattern) needs -noout: a warped
+    mosaic is meaningless."""
     words = list(words)
     if words and words[0] == "register":
         words = words[1:]
@@ -796,8 +823,12 @@ def parse_register_command(words) -> RegisterCommand:
             if o[5:] != "moments" and o[5:] not in PSF_PROFILES:
                 raise ValueError(f"Unknown PSF profile {o[5:]}, aborting.")
             cmd.psf = o[5:]
+        elif o.startswith("-cfa="):
+            cmd.cfa = _parse_cfa_option(o[5:])
         else:
             raise ValueError(f"Unexpected argument to register `{o}', aborting.")
+    if cmd.cfa is not None and not cmd.noout:
+        raise ValueError("-cfa= needs -noout: CFA frames are not warped (seqapplyreg -drizzle -cfa= drizzles them)")
     return cmd
 
 
@@ -814,14 +845,16 @@ def _seq_reference(path: str) -> int:
 
 def _frame_io(d, name, fixed, layer, dev):
     """(read, upload) of a regular FITS sequence: read(num) gives one frame's
-    plane (layer `layer` of RGB frames), upload(host) a device tensor (WORD
-    frames as 16-bit storage)."""
+    plane (layer `layer` of RGB frames; whole=True: the frame as the file
+    holds it), upload(host) a device tensor (WORD frames as 16-bit storage)."""
     import os
     import torch
     from .sequence import frame_name, read_fits
 
-    def read(num):
+    def read(num, whole=False):
         a = read_fits(os.path.join(d, frame_name(name, num, fixed)))
+        if whole:
+            return a
         if a.ndim == 3:
             if layer >= a.shape[0]:
                 raise ValueError("-layer= is outside the frames' layers")
@@ -874,8 +907,12 @@ def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
     consecutively) with their .seq (identity H).  Stacking a
     -noout sequence whose H are more than translations needs that output:
     the .seq reader takes h02 / h12 only.  -psf=gaussian|moffat fits every
-    star as register_stars(psf=) does.  Returns (path of the .seq written
-    last, Hs, info)."""
+    star as register_stars(psf=) does.  With -cfa=PATTERN (one-layer mosaics;
+    the pattern comes from the command line because this FITS reader keeps no
+    BAYERPAT) the stars are looked for on a device copy of every frame passed
+    through interpolate_nongreen, as Siril does on CFA data; the frames on
+    disk are not touched.  Returns (path of the .seq written last, Hs,
+    info)."""
     import os
     import torch
     from .calibration import _read_seq
@@ -895,12 +932,17 @@ def run_register(line, ctx=None, max_batch_bytes: int = 1 << 30):
 
     read, upload = _frame_io(d, name, fixed, cmd.layer, dev)
 
+    if cmd.cfa is not None and read(nums[0], whole=True).ndim != 2:
+        raise ValueError("-cfa= needs one-layer frames")
     first = read(nums[0])
     h, w = first.shape
     batch = max(1, int(max_batch_bytes // (h * w * 4)))
     stars, bkg, fits = [], [], []
     for b0 in range(0, n, batch):
         t = upload(np.stack([read(num) for num in nums[b0:b0 + batch]]))
+        if cmd.cfa is not None:                       # the upload is the copy: the files stay as they are
+            for k in range(t.shape[0]):
+                interpolate_nongreen(t[k], cmd.cfa, ctx)
         bg, noise = frame_background(t, ctx)
         found = find_stars(t, ctx=ctx, bg=bg, noise=noise, max_stars=cmd.maxstars)
         if cmd.psf != "moments":
@@ -946,6 +988,7 @@ class SeqApplyRegCommand:
         self.pixfrac = 1.0
         self.kernel = "square"
         self.flat = None
+        self.cfa = None
         self.interp = OPENCV_LANCZOS4
         self.clamp = True
         self.prefix = "r_"
@@ -954,8 +997,8 @@ class SeqApplyRegCommand:
 def parse_seqapplyreg_command(words) -> SeqApplyRegCommand:
     """`seqapplyreg <seq> [-layer=] [-prefix=r_] [-interp=ne|li|cu|ar|la]
     [-noclamp] | -drizzle [-scale=1] [-pixfrac=1] [-kernel=point|turbo|square]
-    [-flat=FILE]`.  The drizzle options need -drizzle, and -drizzle takes no
-    interpolation."""
+    [-flat=FILE] [-cfa=RGGB|BGGR|GBRG|GRBG|<36 letters>]`.  The drizzle options
+    need -drizzle, and -drizzle takes no interpolation."""
     words = list(words)
     if words and words[0] == "seqapplyreg":
         words = words[1:]
@@ -989,6 +1032,9 @@ def parse_seqapplyreg_command(words) -> SeqApplyRegCommand:
             cmd.flat = o[6:]
             if not cmd.flat:
                 raise ValueError("Missing file name after -flat=")
+            drizzle_only.append(o)
+        elif o.startswith("-cfa="):
+            cmd.cfa = _parse_cfa_option(o[5:])
             drizzle_only.append(o)
         elif o.startswith("-interp="):
             if o[8:] not in INTERPOLATIONS:
@@ -1063,7 +1109,13 @@ def run_seqapplyreg(line, ctx=None, max_batch_bytes: int = 1 << 30):
     their weight planes go to drizztmp/oweight_<prefix><name>NNNNN.fit beside
     them, and the new .seq (identity H, registration values carried over)
     has its drizzle_flag set.  -flat= weights the input pixels by a master
-    flat over its mean.  Returns (path of the new .seq, Hs, info)."""
+    flat over its mean.  With -cfa=PATTERN the frames are colour-filter-array
+    mosaics (one layer, else ValueError): every input pixel lands in the plane
+    of its own colour only (drizzle_frames(cfa=)), the frames and their weight
+    files have three layers (R, G, B) and the .seq says nb_layers 3, so that
+    `stack` weighs every layer by its own plane.  The pattern is given on the
+    command line because this FITS reader keeps no BAYERPAT.  Returns (path
+    of the new .seq, Hs, info)."""
     import os
     import torch
     from .calibration import INV_USHRT_MAX, _master_file, _read_seq
@@ -1087,6 +1139,8 @@ def run_seqapplyreg(line, ctx=None, max_batch_bytes: int = 1 << 30):
     ctx = ctx or Context(0)
     dev = torch.device("cuda", ctx.device)
     read, upload = _frame_io(d, name, fixed, cmd.layer, dev)
+    if cmd.cfa is not None and read(nums[0], whole=True).ndim != 2:
+        raise ValueError("-cfa= needs one-layer frames")
     h, w = read(nums[0]).shape
     info = dict(registered=np.array([f in good for f in range(n)]))
     if not cmd.drizzle:
@@ -1102,8 +1156,9 @@ def run_seqapplyreg(line, ctx=None, max_batch_bytes: int = 1 << 30):
         if flat.shape != (h, w):
             raise ValueError("-flat= does not have the frames' size")
         pw = torch.from_numpy(drizzle_flat_weights(flat)).to(dev)
-    # device bytes per frame: the input plane and the two output planes of scale^2 its pixels
-    per = max(1, int(max_batch_bytes // (h * w * 4 + 2 * ow * oh * 4)) - 1)   # - 1: the reference frame's slot
+    # device bytes per frame: the input plane and the two output planes (CFA: six) of scale^2 its pixels
+    nout = 2 if cmd.cfa is None else 6
+    per = max(1, int(max_batch_bytes // (h * w * 4 + nout * ow * oh * 4)) - 1)   # - 1: the reference frame's slot
     os.makedirs(os.path.join(d, "drizztmp"), exist_ok=True)
     tiles = [0, 0]
     for b0 in range(0, len(good), per):
@@ -1111,7 +1166,7 @@ def run_seqapplyreg(line, ctx=None, max_batch_bytes: int = 1 << 30):
         idx = part if ref_index in part else part + [ref_index]
         t = upload(np.stack([read(nums[f]) for f in idx]))
         img, wts = drizzle_frames(t, Hs[idx], idx.index(ref_index), cmd.scale, cmd.pixfrac, cmd.kernel,
-                                  pixel_weights=pw, ctx=ctx)
+                                  pixel_weights=pw, ctx=ctx, cfa=cmd.cfa)
         st = drizzle_last_tiles(ctx)
         tiles = [tiles[0] + st[0], tiles[1] + st[1]]
         img, wts = img.cpu().numpy(), wts.cpu().numpy()
@@ -1125,6 +1180,7 @@ def run_seqapplyreg(line, ctx=None, max_batch_bytes: int = 1 << 30):
     out_seq = os.path.join(d, cmd.prefix + name + ".seq")
     write_seq(out_seq, cmd.prefix + name, len(good), beg=nums[0], fixed=fixed, reference=good.index(ref_index),
               homographies=np.tile(np.eye(3), (len(good), 1, 1)), reg_layer=cmd.layer, drizzle=True,
+              nb_layers=1 if cmd.cfa is None else 3,
               **{k: v[good] for k, v in regdata.items()})
     info.update(tiles=tuple(tiles), size=(ow, oh))
     return out_seq, Hs, info
