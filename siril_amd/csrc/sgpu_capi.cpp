@@ -300,7 +300,7 @@ long sgpu_last_exact_pixels(sgpu_context *c) {
     if (!c->fb_count.p) return 0;
     if (hipMemcpy(&n, c->fb_count.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
         return SGPU_NO_DEVICE;
-    if (c->wz_cnt.p) {   // the moment path's per-chunk exact pixels (stack_sorted_inst.h)
+    if (c->wz_cnt.p) {   // the moment path's per-chunk exact pixels (stack_wz_launch.h)
         int t = 0;
         if (hipMemcpy(&t, (int *)c->wz_cnt.p + 2 * sgpu::kWzMaxChunks, sizeof(int), hipMemcpyDeviceToHost) !=
             hipSuccess)
@@ -515,20 +515,24 @@ int run_launch_body(sgpu_context *c, KParams k, bool has_shift) {
     HIP_TRY(hipMemsetAsync(k.fb_count, 0, sizeof(int), s));
     // (the total of the chunks' exact pixels and the two deferral totals behind it)
     if (c->wz_cnt.p) HIP_TRY(hipMemsetAsync((int *)c->wz_cnt.p + 2 * sgpu::kWzMaxChunks, 0, 3 * sizeof(int), s));
-    // the WINSORIZED moment path's fallback list and record workspace
-    // (stack_wz.h); SGPU_WZ=0 / 1 / 2 (default) / 3 / 4: off / one kernel /
-    // two kernels (prep and rounds overlapped on two streams at N <= 128) /
-    // always overlapped / never; SGPU_WZ_RW: the rounds kernel's form (A/B)
-    // 7: mode 2 with the prep and the capped rounds head fused into one kernel
-    // wherever that kernel exists (float, N = 65..128; every other shape runs
-    // mode 2).  Unset: fused where it measured clearly faster (wz_fused_auto),
-    // mode 2 elsewhere; SGPU_WZ=2 is the two-kernel path everywhere.
-    static const int wz_env = std::getenv("SGPU_WZ") ? std::atoi(std::getenv("SGPU_WZ")) : -1;
-    static const int wz_mode = wz_env < 0 || wz_env == 7 ? 2 : wz_env;
-    static const int wz_rw = std::getenv("SGPU_WZ_RW") ? std::atoi(std::getenv("SGPU_WZ_RW")) : 64;
-    k.wz_mode = wz_mode;
-    k.wz_fused = wz_env == 7 ? 1 : (wz_env < 0 ? 2 : 0);
-    k.wz_rw = wz_rw;
+    // the WINSORIZED moment path (stack_wz_launch.h): SGPU_WZ unset -- prep
+    // and capped rounds head fused into one kernel where that measured
+    // clearly faster (wz_fused_auto), two kernels elsewhere; 2: two kernels
+    // everywhere; 7: fused wherever the kernel exists (float, N = 65..128);
+    // 4: two kernels on one stream with the tails after the last chunk (the
+    // per-kernel times of a profile); 0: off, the register-resident kernel.
+    // Any other value is 2.
+    static const sgpu::WzForm wz_form = [] {
+        const char *e = std::getenv("SGPU_WZ");
+        if (!e) return sgpu::kWzAuto;
+        switch (std::atoi(e)) {
+            case 0: return sgpu::kWzSortedOnly;
+            case 4: return sgpu::kWzSerial;
+            case 7: return sgpu::kWzFused;
+            default: return sgpu::kWzTwoKernel;
+        }
+    }();
+    k.wz_form = wz_form;
     // NO_REJEC mean (stack_mean.hip): fb2_list collects the pixels whose float
     // mean the kernel cannot prove independent of the summation order
     if (!k.frames16 && k.rtype == SGPU_NO_REJEC) {
@@ -538,13 +542,13 @@ int run_launch_body(sgpu_context *c, KParams k, bool has_shift) {
         HIP_TRY(hipMemsetAsync(k.fb2_count, 0, sizeof(int), s));
     }
     c->last_mean = k.rtype == SGPU_NO_REJEC && !k.frames16;
-    if (k.rtype == SGPU_WINSORIZED && wz_mode) {
+    if (k.rtype == SGPU_WINSORIZED && wz_form != sgpu::kWzSortedOnly) {
         if ((r = c->fb2_list.ensure(k.npix * sizeof(int))) || (r = c->fb2_count.ensure(sizeof(int)))) return r;
         k.fb2_list = (int *)c->fb2_list.p;
         k.fb2_count = (int *)c->fb2_count.p;
         HIP_TRY(hipMemsetAsync(k.fb2_count, 0, sizeof(int), s));
         // workspace: two buffers of rank records (R slots + moments, meta,
-        // round state, lists per pixel; stack_sorted_inst.h), at most 2 GiB
+        // round state, lists per pixel; stack_wz_launch.h), at most 2 GiB
         // and no more than this launch's pixels need
         const int npw = sorted_capacity(N);
         const long long R = npw <= 128 ? 64 : npw / 2 + 16;
@@ -554,7 +558,6 @@ int run_launch_body(sgpu_context *c, KParams k, bool has_shift) {
         k.wz_chunk = chunk;
         // per-chunk tails (fallback sorted + exact kernels of a chunk on a third
         // stream, under the next chunks' work): counters zeroed per launch
-        static const bool tails = !std::getenv("SGPU_WZ_TAILS") || std::atoi(std::getenv("SGPU_WZ_TAILS")) != 0;
         // split rounds (stack_wz.h): SGPU_WZ_SPLIT = rounds cap of the head pass
         // (default 2; 0: the single nest); its stripe counters and the two
         // deferral totals live behind the chunk counters (sgpu_kparams.h)
@@ -562,7 +565,7 @@ int run_launch_body(sgpu_context *c, KParams k, bool has_shift) {
         if (c->wz_cnt.ensure(sgpu::kWzCntInts * sizeof(int)) == SGPU_OK) {
             int *cb = (int *)c->wz_cnt.p;
             HIP_TRY(hipMemsetAsync(cb, 0, (sgpu::kWzDefOff + 2) * sizeof(int), s));
-            if (tails) k.wz_tcnt = cb;
+            k.wz_tcnt = cb;
             k.wz_split = split > 0 ? split : 0;
             k.wz_scnt = cb + sgpu::kWzScntOff;
             k.wz_def = cb + sgpu::kWzDefOff;

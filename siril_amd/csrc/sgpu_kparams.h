@@ -17,6 +17,15 @@ enum Normalization : int {
     MULTIPLICATIVE_SCALING = 4
 };
 
+// Forms of the WINSORIZED moment path (stack_wz_launch.h), from SGPU_WZ
+enum WzForm : int {
+    kWzAuto = 0,        // unset: fused where it measured faster (wz_fused_auto), two kernels elsewhere
+    kWzTwoKernel,       // 2 (and any other value): prep and rounds kernels everywhere
+    kWzFused,           // 7: prep and capped rounds head in one kernel wherever it exists (float, N = 65..128)
+    kWzSerial,          // 4: two kernels on one stream, tails after the last chunk (per-kernel times of a profile)
+    kWzSortedOnly       // 0: no moment path, the register-resident sorted kernel
+};
+
 struct KParams {
     const float *frames;        // frame-major block: frames[f*frame_stride + y*W + x]
     long long frame_stride;     // elements between frames
@@ -42,28 +51,24 @@ struct KParams {
     int *fb_count;              // number of entries in fb_list
     int *fb2_list;              // WINSORIZED moment path: pixels for the register-resident sorted kernel
     int *fb2_count;             // number of entries in fb2_list
-    // WINSORIZED two-kernel moment path (stack_wz.h): pixels [wz_pix0,
+    // WINSORIZED moment path (stack_wz.h): pixels [wz_pix0,
     // wz_pix0 + wz_cnt) of this launch, their rank records (slot-major,
     // stride wz_cnt), window moments [2][wz_cnt] and packed bounds / routes
     long long wz_pix0, wz_cnt;
     float *wz_ranks;
     double *wz_mom;
     int *wz_meta;
-    void *wz_state;             // round-wise rounds: WzState per pixel of the chunk
-    int *wz_list_in, *wz_list_out;   // pixels (chunk-local) entering / leaving the round
-    int *wz_lcount;             // [0]: pixels in wz_list_in, [1]: appended to wz_list_out
-    void *wz_ws;                // workspace the launcher carves these from (two-kernel form), or null
+    void *wz_state;             // split rounds: WzState per pixel of the chunk, written by the head for the pixels
+                                // it defers and carried from tail pass to tail pass
+    void *wz_ws;                // workspace the launcher carves these from (stack_wz_launch.h), or null
     long long wz_ws_bytes;
-    long long wz_chunk;         // two-kernel form: at most this many pixels per chunk (0: as the workspace allows)
-    int *wz_tcnt;               // overlapped form: 2 counters per chunk (fb2, fb) + [kWzMaxChunks*2] the total
+    long long wz_chunk;         // at most this many pixels per chunk (0: as the workspace allows)
+    int *wz_tcnt;               // overlapped and fused forms: 2 counters per chunk (fb2, fb) + [kWzMaxChunks*2] the total
                                 // of the chunks' exact-kernel pixels, or null (tails after the last chunk)
-    int wz_mode;                // 0 register-resident kernel only, 1 moment path in one kernel (LDS), 2 two kernels
-    int wz_fused;               // float, N = 65..128: prep and capped head in one kernel -- 0 never, 1 always (SGPU_WZ=7),
-                                // 2 where it measured faster (SGPU_WZ unset; stack_sorted_inst.h wz_fused_auto)
+    WzForm wz_form;             // which kernels and streams a WINSORIZED launch of 65..1024 samples takes
     int wz_split;               // LDS rounds, float, N <= 128: rounds cap of the head pass (SGPU_WZ_SPLIT; 0: one nest)
     int *wz_scnt;               // split: stripe counters of the two deferral lists [2][kWzStripes * 16], or null
     int *wz_def;                // split: [2] pixels that entered tail pass 1 / 2 (sgpu_last_wz_deferred), or null
-    int wz_rw;                  // two-kernel form: rounds kernel -- 64 ranks staged in LDS (default, N <= 128), 4 / 5 / 6 global reads at that occupancy, 100 round-wise
     float *scratch;             // fallback kernel scratch
     long long scratch_threads;  // number of fallback threads the scratch covers
     // DATA_USHORT sequences (apply_rejection_ushort path)

@@ -46,26 +46,12 @@
 #ifndef SGPU_GW1024_LOOP
 #define SGPU_GW1024_LOOP 16, 3
 #endif
-// The moment path's float prep kernel at NP = 128 has its own lanes per pixel
-// (the rounds kernels take it as a template argument; the fallback sorted
-// kernel keeps SGPU_GW128_LOOP's G): 4 (E = 32 slots per lane), 2 (E = 64) or
-// 1 (the whole column in one lane: k_stack_wz_prep1, stack_wz.h), for
-// unshifted frames and for shifted / normalized ones (XF) separately.
-// Its occupancy target -- waves per SIMD the register allocation must allow
-// -- per form: SGPU_WZ_PREP_W128 for four lanes, _G2 for two, _G1 for one.
-#ifndef SGPU_WZ_PREP_G128
-#define SGPU_WZ_PREP_G128 1
-#endif
-#ifndef SGPU_WZ_PREP_G128_XF
-#define SGPU_WZ_PREP_G128_XF 1
-#endif
-#ifndef SGPU_WZ_PREP_W128
-#define SGPU_WZ_PREP_W128 6
-#endif
-#ifndef SGPU_WZ_PREP_W128_G2
-#define SGPU_WZ_PREP_W128_G2 4
-#endif
-// (one lane: 159-162 VGPRs, three waves per SIMD, with either 2 or 3 here)
+// The moment path's float prep kernel at NP = 128 runs one lane per pixel (the
+// whole column in one lane: k_stack_wz_prep1, stack_wz.h; the rounds kernels
+// take the lanes per pixel as a template argument, the fallback sorted kernel
+// keeps SGPU_GW128_LOOP's G).  Its occupancy target -- waves per SIMD the
+// register allocation must allow:
+// (159-162 VGPRs, three waves per SIMD, with either 2 or 3 here)
 #ifndef SGPU_WZ_PREP_W128_G1
 #define SGPU_WZ_PREP_W128_G1 3
 #endif
@@ -73,14 +59,3 @@
 #ifndef SGPU_WZ_FUSED_W128
 #define SGPU_WZ_FUSED_W128 3
 #endif
-// real-slot bounds of the four-lane prep (stack_sorted_rs128.hip): first
-// bound and step; rs_pick_prep4 takes the smallest one >= ceil(N / 4)
-#ifndef SGPU_WZ_PREP4_RS0
-#define SGPU_WZ_PREP4_RS0 20
-#endif
-#ifndef SGPU_WZ_PREP4_RSSTEP
-#define SGPU_WZ_PREP4_RSSTEP 4
-#endif
-static_assert((SGPU_WZ_PREP_G128 == 1 || SGPU_WZ_PREP_G128 == 2 || SGPU_WZ_PREP_G128 == 4) &&
-              (SGPU_WZ_PREP_G128_XF == 1 || SGPU_WZ_PREP_G128_XF == 2 || SGPU_WZ_PREP_G128_XF == 4),
-              "prep kernel: 1, 2 or 4 lanes per pixel");

@@ -171,7 +171,7 @@ struct RankStore {
     // regions then hold exactly what store() puts there (plus +Inf in slots of
     // ranks >= kept, which fetch never reads).  Needs NP * stride * 4 <=
     // 2^32 (negative slots >= -NP stay above the record count), which the
-    // launcher enforces (stack_sorted_inst.h).  (Host builds, tests/hostsim:
+    // launcher enforces (stack_wz_launch.h).  (Host builds, tests/hostsim:
     // the descriptor's range check restated per store -- drop().)
     SG_HD void drop(int region0, int size, int slot, float x) {
         if (slot >= 0 && slot < size) base[(long long)(region0 + slot) * stride + p] = x;
@@ -297,7 +297,7 @@ struct RankStore {
         const int slot = lo_ok ? r : hi_ok ? KT + KM + r - (kept - KT) : KT + r - (kept / 2 - KM / 2);
         const bool ok = lo_ok || hi_ok || mid_ok;
         // slot < R and stride = the chunk's pixels < 2^23 with R * stride <
-        // 2^32 (both enforced by the launcher, stack_sorted_inst.h): one
+        // 2^32 (both enforced by the launcher, stack_wz_launch.h): one
         // full-rate 24-bit multiply whose 32-bit product cannot wrap; the
         // pixel's base address is loop-invariant (a 64-bit multiply per fetch
         // was quarter-rate work)
@@ -392,8 +392,8 @@ SG_HD float median_from(float a, float b, int n) {
     return (float)(((double)a + b) / 2.0);
 }
 
-// Rejection state of one pixel between rounds (kept in HBM between the
-// launches of the round-wise rounds kernel) and the per-pixel constants the
+// Rejection state of one pixel between rounds (kept in HBM between the head
+// and the tail passes of the split rounds) and the per-pixel constants the
 // rounds read (recomputed from the stored ranks at every launch).
 struct WzState {
     double W1, W2;           // window moments about c0
@@ -620,8 +620,8 @@ SG_HD int wz_start(const RS &rs, int kept, double W1, double W2, float c0, int m
 // pass visited.  (A one-phase-per-call state machine with lane refill, so
 // that lanes do not wait for the slowest pixel of their wave, was built and
 // measured slower: 25.1 vs 17.1 ms for config 2 -- every trip pays every
-// phase some lane is in.  The round-wise launches below refill at round
-// granularity instead.)
+// phase some lane is in.  The split rounds below compact the pixels that
+// outlast the head's cap instead.)
 template <int U16 = 0, class RS>
 SG_HD int wz_finish(const RS &rs, int kept, double W1, double W2, float c0, int m, float slo_, float shi_,
                     PixOut &o) {
@@ -753,7 +753,8 @@ SG_HD int wz_prepare(float (&v)[NP / G], int g, int kept, int kmin, int N, RankS
     return 0;
 }
 
-// One pixel after the gather (single-kernel form: LDS rank store; hostsim).
+// One pixel after the gather, prep and rounds in one call on an LDS-style
+// rank store: the host simulation's entry (tests/hostsim); no kernel calls it.
 template <int NP, int G, int U16 = 0>
 SG_HD int wz_pixel(float (&v)[NP / G], int g, int kept, int kmin, int N, float slo_, float shi_,
                    RankStore<NP, G> &rs, PixOut &o) {
@@ -765,70 +766,12 @@ SG_HD int wz_pixel(float (&v)[NP / G], int g, int kept, int kmin, int N, float s
     return wz_finish<U16>(rs, kept, W1, W2, c0, G * E, slo_, shi_, o);
 }
 
-// The kernel: one pixel per group of G lanes (interleaved layout after the
-// sort), 4 waves per block.
-template <int NP, int G, int XF, int W>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
-void k_stack_wz(KParams p) {
-    constexpr int E = NP / G;
-    using RS = RankStore<NP, G>;
-    __shared__ float s_rank[4 * RS::PW * RS::R];
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long pix = gid / G;
-    const int g = (int)(gid % G);
-    int rl = 0, rh = 0;
-    if (pix < p.npix) {       // group-uniform
-        const int x = (int)(pix % p.W);
-        int kept = 0, bad = 0;
-        RS rs;
-        rs.base = s_rank + (threadIdx.x >> 6) * (RS::PW * RS::R);
-        rs.stride = RS::PW;
-        rs.p = (int)(threadIdx.x & 63) / G;
-        PixOut o;
-        int route;
-        {
-            float v[E];
-            gather_column<XF, E, G, true>(p, v, pix, x, g, kept, bad);
-            bad = gsum_t<G>(bad);
-            kept = gsum_t<G>(kept);
-            // the wave's smallest kept (uniform: the rank store's slot
-            // loops; any value keeps the store and its reads consistent)
-            int kmin = kept;
-#pragma unroll
-            for (int lm = 32; lm >= 1; lm >>= 1) kmin = min(kmin, __shfl_xor(kmin, lm, 64));
-            kmin = __builtin_amdgcn_readfirstlane(kmin);
-            route = bad ? 2 : wz_pixel<NP, G>(v, g, kept, kmin, p.nframes, p.sig0, p.sig1, rs, o);
-        }
-        if (route == 1) {
-            if (g == 0) {
-                const int slot = wave_append(p.fb2_count, true);
-                p.fb2_list[slot] = (int)pix;
-            }
-        } else if (route == 2) {
-            if (g == 0) {
-                const int slot = wave_append(p.fb_count, true);
-                p.fb_list[slot] = (int)pix;
-            }
-        } else if (g == 0) {
-            double res = o.res;
-            if (is_weighted(p)) res = weighted_mean(p, pix, x, o.pmin, o.pmax, o.nkept);
-            write_result(p, pix, res, o.rl, o.rh);
-            rl = o.rl;
-            rh = o.rh;
-        }
-    }
-    add_counts(p, rl, rh);
-}
-
-// ---------------------------------------------------------------- one lane per pixel, column in LDS
-// SGPU_WZ=6: one pixel per lane (E = NP samples in VGPRs, G = 1: no
-// cross-lane merge in the sort), the WHOLE sorted column written to LDS
-// (lane-major rows of LS = N | 1 floats: lanes reading the same rank hit
-// different banks), moments from the registers, then every round reads its
-// ranks from LDS -- every rank is available (no stored-range fallbacks) and
-// no rank record ever goes to HBM (traffic = the frames + the output).
+// The rounds on a rank store that holds EVERY rank of the sorted column (no
+// stored-range fallbacks): the host simulation runs wz_finish on it against
+// the oracle (tests/hostsim sim_wz1_pixels), which checks the rounds apart
+// from RankStore's ranges.  No kernel uses it.
 struct ColStore {
-    const float *base;                   // this lane's row: rank r at base[r]
+    const float *base;                   // the pixel's row: rank r at base[r]
     int kept;
     SG_HD bool fetch(int r, float &x) const {
         const bool ok = r >= 0 && r < kept;
@@ -843,8 +786,7 @@ struct ColStore {
 // From the sorted column (ranks 0..N-1 in row[], missing samples +Inf at
 // ranks >= kept) to the result: first median (median_win's rounding), the
 // window moments about it in rank order (accumulator q takes ranks = q mod
-// SGPU_NACC; ranks >= kept add 0), then every round on ColStore.  Shared by
-// k_stack_wz1 (row in LDS) and the host simulation (tests/hostsim).
+// SGPU_NACC; ranks >= kept add 0), then every round on ColStore.
 SG_HD int wz1_pixel(const float *row, int kept, int N, float sig0, float sig1, PixOut &o) {
     const int k2 = kept / 2;
     const float c0 = median_from(row[(kept & 1) ? k2 : k2 - 1], row[k2], kept);
@@ -875,66 +817,8 @@ SG_HD int wz1_pixel(const float *row, int kept, int N, float sig0, float sig1, P
     return wz_finish(cs, kept, W1, W2, c0, el, sig0, sig1, o);
 }
 
-template <int NP, int XF, int W>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W, 8)))
-void k_stack_wz1(KParams p, int LS) {
-    extern __shared__ float s_col[];
-    const int lane = (int)threadIdx.x;
-    const long long pix = (long long)blockIdx.x * 64 + lane;
-    const bool live = pix < p.npix;
-    const int N = p.nframes;
-    int rl = 0, rh = 0;
-    int route = 2;
-    PixOut o;
-    int kept = 0, bad = 0;
-    float *row = s_col + lane * LS;
-    {
-        // the column lives in VGPRs only for the gather and the sort; it
-        // leaves for LDS right after (keeps the register peak at the sort's)
-        float v[NP];
-        // a dead lane gathers the block's first pixel (valid addresses) and
-        // is discarded below; every lane runs the sort (wave-uniform code)
-        const long long gp = live ? pix : (long long)blockIdx.x * 64;
-        gather_column<XF, NP, 1, true>(p, v, gp, (int)(gp % p.W), 0, kept, bad);
-        sort_col<NP, 1>(v, 0);
-#if defined(__HIP_DEVICE_COMPILE__)
-        // no scheduling of the stores into the sort network: interleaved,
-        // they stretch the live ranges past the 256 VGPRs (66 spilled)
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-        // every slot is stored (no per-slot branches: they blew the register
-        // allocation up); the padding slots e >= N all land on the row's
-        // spare word row[N] (LS > N)
-#pragma unroll
-        for (int e = 0; e < NP; e++) row[e < N ? e : N] = v[e];
-    }
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
-    if (live) {
-        route = (!bad && kept > 0) ? wz1_pixel(row, kept, N, p.sig0, p.sig1, o)
-                                   : 2;   // NaN / Inf, or kept == 0: the exact kernel
-        if (route == 1) {
-            const int slot = wave_append(p.fb2_count, true);
-            p.fb2_list[slot] = (int)pix;
-        } else if (route == 2) {
-            const int slot = wave_append(p.fb_count, true);
-            p.fb_list[slot] = (int)pix;
-        } else {
-            double res = o.res;
-            if (is_weighted(p)) res = weighted_mean(p, pix, (int)(pix % p.W), o.pmin, o.pmax, o.nkept);
-            write_result(p, pix, res, o.rl, o.rh);
-            rl = o.rl;
-            rh = o.rh;
-        }
-    }
-    add_counts(p, rl, rh);
-}
-
 // ---------------------------------------------------------------- two-kernel form
-// The same path split where its needs split: k_stack_wz_prep (gather, sort,
+// The path split where its needs split: k_stack_wz_prep (gather, sort,
 // rank store, moments: the register-wide part, G lanes per pixel) writes a
 // record per pixel to HBM -- ranks slot-major (lanes of a wave read
 // neighbouring words), moments and packed bounds -- and k_stack_wz_rounds
@@ -1140,9 +1024,10 @@ void k_stack_wz_prep1(KParams p) {
 
 // PG (here and in the rounds kernels below): the lanes per pixel of the prep
 // kernel that wrote the records -- PG * el slots went into its moments, the
-// term count its error bounds take (the launcher passes the prep's own G)
-template <int NP, int W, int U16 = 0, int PG = NP / 64>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
+// term count its error bounds take (the launcher passes the prep's own G).
+// Global rank reads, five waves per SIMD: N > 128 and the 16-bit path.
+template <int NP, int U16 = 0, int PG = NP / 64>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8)))
 void k_stack_wz_rounds(KParams p) {
     using RS = RankStore<NP, 1>;
     const long long loc = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1185,98 +1070,8 @@ void k_stack_wz_rounds(KParams p) {
     add_counts(p, rl, rh);
 }
 
-// Round-wise rounds (SGPU_WZ_RW=100): one launch per rejection round.  The
-// pixels of a wave take 1-6 rounds of 1-16 clamp iterations each; run as one
-// loop nest, a wave pays the sum over rounds of its slowest pixel, with the
-// finished pixels' lanes idle.  Here launch `pass` runs one round for every
-// pixel still going (pass 0: all of the chunk) and appends the pixels that
-// need another round to wz_list_out (one atomic per wave), their state to
-// wz_state; the last pass (`last`) runs every remaining round.  A model of the
-// bench data's round / iteration counts gives 0.65 active lanes per trip
-// against 0.44 for the nest.
-// (wave_append: stack_sorted_impl.h)
-
-template <int NP, int W, int PG = NP / 64>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
-void k_stack_wz_round(KParams p, int pass, int last) {
-    using RS = RankStore<NP, 1>;
-    constexpr int G = PG;                      // the prep kernel's lanes per pixel
-    const long long n = pass == 0 ? p.wz_cnt : (long long)p.wz_lcount[0];
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    int rl = 0, rh = 0;
-    // tiles of the launch: the loop trip count is wave-uniform (wave_append)
-    for (long long t0 = (long long)blockIdx.x * blockDim.x; t0 < n; t0 += stride) {
-        const long long i = t0 + threadIdx.x;
-        const bool live = i < n;
-        bool again = false;
-        long long loc = 0;
-        if (live) {
-            loc = pass == 0 ? i : (long long)p.wz_list_in[i];
-            const long long pix = p.wz_pix0 + loc;
-            const int4 m = reinterpret_cast<const int4 *>(p.wz_meta)[loc];
-            int route = 2;
-            PixOut o;
-            WzConst k;
-            WzState st;
-            if (m.x > 0) {
-                RS rs;
-                rs.base = p.wz_ranks;
-                rs.stride = p.wz_cnt;
-                rs.p = loc;
-                rs.kept = m.x;
-                rs.hi0 = m.y;
-                rs.mid0 = m.z;
-                rs.mid1 = m.w;
-                const int N = p.nframes;
-                const int el = (((N + G - 1) / G) + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1);
-                const float c0 = (float)p.wz_mom[2 * p.wz_cnt + loc];
-                if (pass == 0) {
-                    route = wz_start(rs, m.x, p.wz_mom[loc], p.wz_mom[p.wz_cnt + loc], c0, G * el, p.sig0, p.sig1,
-                                     k, st, o);
-                } else {
-                    float ymax, vmin;
-                    route = wz_consts(rs, m.x, c0, G * el, p.sig0, p.sig1, k, ymax, vmin);
-                    st = reinterpret_cast<const WzState *>(p.wz_state)[loc];
-                    o.fallback = 0;
-                }
-                if (route == 3) {
-                    route = 0;                 // kept == 1: o is the result
-                } else if (route == 0) {
-                    bool more = true;
-                    do route = wz_round(rs, k, st, more);   // one call site: one inlined copy
-                    while (last && more && !route);
-                    if (!route && more) {
-                        again = true;
-                        reinterpret_cast<WzState *>(p.wz_state)[loc] = st;
-                    } else if (!route) {
-                        route = wz_final(rs, k, st, o);
-                    }
-                }
-            }
-            if (!again) {
-                if (route == 1) {
-                    const int slot = wave_append(p.fb2_count, true);
-                    p.fb2_list[slot] = (int)pix;
-                } else if (route == 2) {
-                    const int slot = wave_append(p.fb_count, true);
-                    p.fb_list[slot] = (int)pix;
-                } else {
-                    double res = o.res;
-                    if (is_weighted(p)) res = weighted_mean(p, pix, (int)(pix % p.W), o.pmin, o.pmax, o.nkept);
-                    write_result(p, pix, res, o.rl, o.rh);
-                    rl += o.rl;
-                    rh += o.rh;
-                }
-            }
-        }
-        const int slot = wave_append(p.wz_lcount + 1, again);
-        if (again) p.wz_list_out[slot] = (int)loc;
-    }
-    add_counts(p, rl, rh);
-}
-
-// Rounds kernel with the rank records staged in LDS (default at N <= 128,
-// SGPU_WZ_RW=64): one wave per block copies its 64 pixels' R rank slots
+// Rounds kernel with the rank records staged in LDS (N <= 128): one wave per
+// block copies its 64 pixels' R rank slots
 // (slot-major rows of the workspace: every copy instruction reads 256
 // contiguous bytes) into LDS, so the dependent rank reads of the rounds
 // (medians, tail walks, clip walks) are LDS round trips instead of L2 / HBM

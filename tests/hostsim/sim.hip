@@ -11,8 +11,9 @@ using namespace sgpu;
 
 // WINSORIZED moment-path routes: [0] answered, [1] sorted path, [2] exact kernel
 static long long sim_wz_route[3];
-// 1: run the moment path the way the round-wise launches do (state saved and
-// the constants rebuilt between rounds)
+// 1: run the moment path with the state saved and the constants rebuilt
+// between rounds -- the sequence k_stack_wz_tail relies on when it resumes a
+// pixel the head deferred, here after every round
 static int sim_roundwise = 0;
 extern "C" void sim_set_roundwise(int on) { sim_roundwise = on; }
 extern "C" void sim_wz_stats(long long *out) {
@@ -53,8 +54,9 @@ static int run(const float *col, int n, const PixCfg &c, double *res, int *rl, i
         if (!sim_roundwise || U16) {
             route = wz_pixel<NP, 1, U16>(w, 0, kept, kept, c.nframes, c.sig0, c.sig1, rs, o);
         } else if constexpr (!U16) {
-            // k_stack_wz_round's decomposition: pass 0 starts the pixel, every
-            // later pass rebuilds the constants and resumes from the saved state
+            // the tail passes' decomposition (k_stack_wz_tail), one round per
+            // pass: pass 0 starts the pixel, every later pass rebuilds the
+            // constants and resumes from the saved state
             double W1, W2;
             float c0;
             route = wz_prepare<NP, 1>(w, 0, kept, kept, c.nframes, rs, W1, W2, c0) ? 2 : 0;
@@ -154,9 +156,9 @@ extern "C" void sim_pixels(int rt, const float *frames, int n, long long ncol, f
     }
 }
 
-// the one-lane-per-pixel fused form (k_stack_wz1, SGPU_WZ=6): the whole
-// sorted column in a row (missing samples +Inf), wz1_pixel; st[j] = route
-// (0 answered, 1 sorted kernel, 2 exact kernel)
+// the rounds on the whole sorted column (stack_wz.h ColStore, every rank
+// stored: no stored-range fallbacks): the column in a row (missing samples
+// +Inf), wz1_pixel; st[j] = route (0 answered, 1 sorted kernel, 2 exact kernel)
 extern "C" void sim_wz1_pixels(const float *frames, int n, long long ncol, float sig0, float sig1, double *res,
                                int *rl, int *rh, int *st) {
     float row[1025];

@@ -142,10 +142,12 @@ def test_winsorized_moment_path_matches_oracle(oracle, hostsim):
 
 
 def test_winsorized_roundwise_decomposition_matches_oracle(oracle, hostsim):
-    """The moment path as the round-wise launches run it (k_stack_wz_round:
-    the pixel's state saved after every round, its constants rebuilt from the
-    stored ranks before the next): the same oracle parity as the one-call
-    form on the benchmark recipe, zeros, ties and heavy tails."""
+    """The save / rebuild-constants / resume sequence the split rounds rest on
+    (stack_wz.h k_stack_wz_tail resumes a pixel the head deferred from its
+    saved WzState after wz_consts has rebuilt the constants from the stored
+    ranks), taken to its limit: the pixel's state saved after every round and
+    its constants rebuilt before the next.  The same oracle parity as the
+    one-call form on the benchmark recipe, zeros, ties and heavy tails."""
     from siril_amd import synth
     rng = np.random.default_rng(41)
     zeros = synth.frames_numpy(100, 2, 1024, seed=22)
@@ -168,8 +170,9 @@ def test_winsorized_roundwise_decomposition_matches_oracle(oracle, hostsim):
 
 
 def test_winsorized_fused_column_path_matches_oracle(oracle, hostsim):
-    """The one-lane-per-pixel fused form (stack_wz.h k_stack_wz1 / wz1_pixel:
-    whole sorted column in LDS, moments in rank order) on the host: every
+    """The rounds on a store that holds every rank of the sorted column
+    (stack_wz.h ColStore / wz1_pixel: moments in rank order, no stored-range
+    fallbacks) on the host: every
     pixel it answers equals the oracle bit for bit (mean and both counts),
     on the benchmark recipe, normalized-looking columns and small N."""
     from siril_amd import synth

@@ -1,7 +1,9 @@
 """The fused prep + rounds kernel of the float WINSORIZED moment path at N =
 65..128 (stack_wz.h: k_stack_wz_fused1, SGPU_WZ=7): every case bit for bit
 against the oracle on result bits, both rejection maps and the totals, under
-the fused mode and under SGPU_WZ=2 (the two-kernel path).
+the fused mode and under SGPU_WZ=2 (the two-kernel path); a subset under the
+two diagnostic modes SGPU_WZ=4 (one stream, tails after the last chunk) and
+SGPU_WZ=0 (the register-resident kernel only).
 
 SGPU_WZ and SGPU_WZ_CHUNK are read once per process, so each mode runs every
 case in one fresh child (this file run as a program) and leaves its outputs in
@@ -220,3 +222,27 @@ def test_many_chunks(runs, refs, mode):
     print("mode", mode, info["chunks"])
     _check(out, "chunks", refs("chunks", True))
     assert info["chunks"]["deferred"][0] > 0
+
+
+DIAG_CASES = ["cols100_s3", "cols65_s1", "cols128_s3", "recipe70_s2", "shift", "weights"]
+
+
+@pytest.mark.parametrize("mode", ["4", "0"])
+def test_diagnostic_modes(runs, refs, mode):
+    """SGPU_WZ=4 (the two kernels on one stream, no per-chunk tails: the
+    per-kernel times of a profile) and SGPU_WZ=0 (no moment path).  Both give
+    the oracle's bits; mode 4 runs mode 2's kernels with the same rounds cap
+    and only the streams differ, so it defers the same pixels."""
+    out, info = runs(mode)
+    outc, infoc = runs(mode, True)
+    for name in DIAG_CASES:
+        print(name, "mode", mode, info[name])
+        _check(out, name, refs(name))
+    print("chunks mode", mode, infoc["chunks"])
+    _check(outc, "chunks", refs("chunks", True))
+    if mode == "4":
+        _, info2 = runs("2")
+        _, info2c = runs("2", True)
+        for name in DIAG_CASES:
+            assert info[name]["deferred"] == info2[name]["deferred"], name
+        assert infoc["chunks"]["deferred"] == info2c["chunks"]["deferred"]

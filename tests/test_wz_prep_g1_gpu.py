@@ -1,5 +1,5 @@
 """One lane per pixel in the float WINSORIZED prep kernel at N <= 128
-(k_stack_wz_prep1, stack_wz.h; stack_sorted_gw.h SGPU_WZ_PREP_G128 = 1): every
+(k_stack_wz_prep1, stack_wz.h; stack_sorted_gw.h SGPU_WZ_PREP_W128_G1): every
 GPU case bit for bit against the oracle on result bits, both rejection maps
 and the totals.
 

@@ -1,13 +1,15 @@
-"""Four lanes per pixel in the float WINSORIZED prep kernel at N <= 128
-(k_stack_wz_prep<128, 4, ...>, E = 32 slots per lane; stack_sorted_gw.h
-SGPU_WZ_PREP_G128): every case bit for bit against the oracle on result bits,
-both rejection maps and the totals.
+"""Oracle parity of the float WINSORIZED moment path's default launch at N =
+65..128: every case bit for bit against the oracle on result bits, both
+rejection maps and the totals.  (Written for a prep kernel with four lanes per
+pixel, since removed; the file keeps its name and its cases, which the
+one-lane prep and the fused kernel now answer.)
 
 N covers the ends of the capacity (65, 128), the benchmark's 100 and both
-sides of every real-slot bound b a build may compile (rs_pick_prep4: b = 20,
-24, 26, 28 -> N = 4b and 4b + 1; 65, 81, 97, 105 and 113 are the buckets'
-lowest N).  Frames are N x 5 x 203: 1 015 pixels, no multiple of the 16
-pixels of a wave, so the last wave has a partial group and dead lanes."""
+sides of every multiple of 16 and of 8 between them that a prep kernel has had
+a real-slot bound at (N = 4b and 4b + 1 for b = 20, 24, 26, 28; 65, 81, 97,
+105 and 113 are the lowest N of those buckets).  Frames are N x 5 x 203: 1 015
+pixels, no multiple of the 64 pixels of a wave, so the last wave has dead
+lanes."""
 import json
 import os
 import subprocess
