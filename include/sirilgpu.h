@@ -675,6 +675,45 @@ int sgpu_subsky_planes_device(sgpu_context *ctx, const void *d_in, int elem_size
  * context's stream; waits for the call): box medians, fit, streaming pass. */
 int sgpu_bkg_last_kernel_ms(sgpu_context *ctx, float ms[3]);
 
+/* ---- a trous wavelets (the `wavelet` and `wrecons` commands) --------------- */
+
+/* Arithmetic: the specification in DESIGN.md 6j (W0-W5), restated in
+ * tests/wavelet_ref.py; parity with a Siril binary is unpinned.  A plane is
+ * width x height samples (elem_size 2: WORD, scaled by 1/65535; 4: float).
+ * nbr_layers = n in 1 .. 6 counts the output planes: n - 1 detail planes
+ * w_0 .. w_{n-2} and the residual c_{n-1}.  type 1: linear taps, 2: B3 spline.
+ * The calls are asynchronous on the context's stream, copy nothing to the host
+ * and keep their intermediate planes in the context's workspace (three float
+ * planes per input plane).  nplanes == 0 does nothing. */
+#define SGPU_WAVELET_MAX_LAYERS 6
+#define SGPU_WAVELET_MAX_LAUNCHES 16
+/* SGPU_OK, or SGPU_BAD_ARGUMENT: nbr_layers outside 1 .. 6, type outside
+ * 1 .. 2, or the largest tap offset (2^(n-1) for type 2, 2^(n-2) for type 1,
+ * 0 for n = 1) above min(width, height) - 1.  Host only. */
+int sgpu_wavelet_check(int width, int height, int nbr_layers, int type);
+/* Transform: plane p at d_in + p*plane_stride samples; its plane k at
+ * d_planes + p*out_image_stride + k*out_plane_stride floats.  The output may
+ * not overlap the input. */
+int sgpu_wavelet_planes_device(sgpu_context *ctx, const void *d_in, int elem_size, int nplanes, int width, int height,
+		long plane_stride, int nbr_layers, int type, float *d_planes, long out_plane_stride,
+		long out_image_stride);
+/* Weighted reconstruction of stored planes (laid out as above):
+ * acc = coef[0]*plane 0, then acc = acc + coef[k]*plane k for ascending k;
+ * image p at d_out + p*out_stride.  No clamp.  Non-finite coefficients and an
+ * output that overlaps the planes return SGPU_BAD_ARGUMENT. */
+int sgpu_wavelet_reconstruct_device(sgpu_context *ctx, const float *d_planes, int nplanes, int width, int height,
+		long plane_stride, long image_stride, int nbr_layers, const float *coef, float *d_out,
+		long out_stride);
+/* Both at once, bit for bit what the two calls above give, without writing a
+ * detail plane: d_out is the accumulator. */
+int sgpu_wrecons_planes_device(sgpu_context *ctx, const void *d_in, int elem_size, int nplanes, int width, int height,
+		long plane_stride, int nbr_layers, int type, const float *coef, float *d_out, long out_stride);
+/* Kernel times of the context's last wavelet call (HIP events between the
+ * launches; waits for the call).  what[k] = 100*form + 10*first scale +
+ * number of scales, form 0: tiled pass, 1: row pass, 2: column pass,
+ * 3: reconstruction of stored planes.  Arrays of SGPU_WAVELET_MAX_LAUNCHES. */
+int sgpu_wavelet_last_kernel_ms(sgpu_context *ctx, float *ms, int *what, int *nlaunches);
+
 /* ---- star detection and star-based global registration ------------------- */
 
 /* Arithmetic: the specification in DESIGN.md 6f, restated in

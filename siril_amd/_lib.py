@@ -51,6 +51,8 @@ EXPORTS = (
     "sgpu_cosmetic_correction_device", "sgpu_dark_optimize_device", "sgpu_calibrate_frames_device",
     "sgpu_bkg_default_params", "sgpu_bkg_grid", "sgpu_subsky_planes_device",
     "sgpu_bkg_last_kernel_ms",
+    "sgpu_wavelet_check", "sgpu_wavelet_planes_device", "sgpu_wavelet_reconstruct_device",
+    "sgpu_wrecons_planes_device", "sgpu_wavelet_last_kernel_ms",
     "sgpu_star_default_params", "sgpu_match_default_params", "sgpu_star_smooth_table", "sgpu_find_stars_device",
     "sgpu_star_last_candidates", "sgpu_star_last_kernel_ms", "sgpu_match_stars",
     "sgpu_psf_default_params", "sgpu_fit_stars_device", "sgpu_psf_last_kernel_ms",
@@ -397,6 +399,16 @@ def lib():
                                                 vp, vp]
         L.sgpu_bkg_last_kernel_ms.restype = i
         L.sgpu_bkg_last_kernel_ms.argtypes = [vp, C.POINTER(f)]
+        L.sgpu_wavelet_check.restype = i
+        L.sgpu_wavelet_check.argtypes = [i, i, i, i]
+        L.sgpu_wavelet_planes_device.restype = i
+        L.sgpu_wavelet_planes_device.argtypes = [vp, vp, i, i, i, i, C.c_long, i, i, vp, C.c_long, C.c_long]
+        L.sgpu_wavelet_reconstruct_device.restype = i
+        L.sgpu_wavelet_reconstruct_device.argtypes = [vp, vp, i, i, i, C.c_long, C.c_long, i, C.POINTER(f), vp, C.c_long]
+        L.sgpu_wrecons_planes_device.restype = i
+        L.sgpu_wrecons_planes_device.argtypes = [vp, vp, i, i, i, i, C.c_long, i, i, C.POINTER(f), vp, C.c_long]
+        L.sgpu_wavelet_last_kernel_ms.restype = i
+        L.sgpu_wavelet_last_kernel_ms.argtypes = [vp, C.POINTER(f), pi, pi]
         L.sgpu_star_default_params.restype = None
         L.sgpu_star_default_params.argtypes = [C.POINTER(StarParams)]
         L.sgpu_match_default_params.restype = None

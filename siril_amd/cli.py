@@ -23,7 +23,13 @@ every input pixel lands in the plane of its own colour, and the frames, the weig
 `python -m siril_amd.cli seqsubsky <seq> <degree> [-samples=20] [-tolerance=1.0] [-nodither] [-prefix=bkg_]`: polynomial
 background extraction of every frame (siril_amd/background.py), degree 1 .. 4, each layer on its own; writes 32-bit
 <prefix><name>NNNNN.fit and the new .seq.  -nodither is accepted (the output is float, nothing is dithered); -rbf and
--smooth= are refused."""
+-smooth= are refused.
+
+`python -m siril_amd.cli wavelet <image> <nbr_layers> <type> [-prefix=]`: the a trous wavelet planes of an image
+(siril_amd/wavelets.py), type 1 linear or 2 B3 spline; writes the nbr_layers planes (the details, then the residual)
+as 32-bit <prefix><stem>_wavelet<k>.fit.  `python -m siril_amd.cli wrecons <image> c1 ... cn [-type=1|2] [-out=FILE]`
+sharpens with them: the planes of an n-layer transform weighted by c1 .. cn and summed, in one fused pass; writes one
+32-bit image, <stem>_wrecons.fit unless -out= names it."""
 import sys
 import time
 
@@ -43,6 +49,18 @@ def main(argv=None):
         out, info = run_seqsubsky(argv)
         print(f"Background extracted to {out} in {time.perf_counter() - t0:.3f} s; sample boxes kept per plane "
               f"{int(info['kept'].min())} .. {int(info['kept'].max())}")
+        return 0
+    if argv and argv[0] == "wavelet":
+        from siril_amd.wavelets import run_wavelet
+        t0 = time.perf_counter()
+        out = run_wavelet(argv)
+        print(f"Wavelet planes written to {out[0]} .. {out[-1]} in {time.perf_counter() - t0:.3f} s")
+        return 0
+    if argv and argv[0] == "wrecons":
+        from siril_amd.wavelets import run_wrecons
+        t0 = time.perf_counter()
+        out = run_wrecons(argv)
+        print(f"Reconstructed to {out} in {time.perf_counter() - t0:.3f} s")
         return 0
     if argv and argv[0] == "register":
         from siril_amd.registration import run_register
