@@ -675,6 +675,48 @@ int sgpu_subsky_planes_device(sgpu_context *ctx, const void *d_in, int elem_size
  * context's stream; waits for the call): box medians, fit, streaming pass. */
 int sgpu_bkg_last_kernel_ms(sgpu_context *ctx, float ms[3]);
 
+/* ---- thin-plate-spline background extraction (the `subsky <image> -rbf` command) ---- */
+
+/* Arithmetic: the specification in DESIGN.md 6k (R0-R7), restated in
+ * tests/bkg_rbf_ref.py; parity with a Siril binary is unpinned.  Grid, box
+ * medians, selection and correction are those of sgpu_subsky_planes_device;
+ * the model is a thin-plate spline through the n kept boxes, phi = r^2 log r
+ * with a constant term, smoothed on the diagonal by lam_rel * mean |phi|,
+ * lam_rel = 1e-4 * 10^(3 (smooth - 0.5)), and evaluated at every pixel in
+ * double. */
+#define SGPU_BKG_RBF_MAX_SAMPLES 1024   /* boxes of the grid, so samples of the spline too */
+/* The refusals of sgpu_subsky_rbf_planes_device (host only): the grid's
+ * (sgpu_bkg_grid), more than SGPU_BKG_RBF_MAX_SAMPLES boxes, a tolerance that
+ * is negative or not finite, smooth outside [0, 1] or not finite. */
+int sgpu_bkg_rbf_check(int width, int height, int samples, double tolerance, double smooth);
+/* As sgpu_subsky_planes_device with the spline for the polynomial: box
+ * medians, one launch (per 256 MiB of systems) that selects, builds and solves
+ * every plane's system of order n + 1 in one workgroup, and the evaluation
+ * fused with the correction; asynchronous, nothing is copied to the host.
+ * d_weights[nplanes * (SGPU_BKG_RBF_MAX_SAMPLES + 1)]: the n weights in the
+ * order of the kept boxes, the constant, then +0.0; d_mean: the mean of the
+ * kept medians; d_status: 0, 1 (no sample box kept) or 2 (the spline system
+ * is singular).  A plane whose status is not 0 is written as its converted
+ * input, its weights and mean are +0.  *lam_rel_out (optional, host) is the
+ * double lam_rel the kernels were given.  A result array may be null; it then
+ * lives in the context until the next call.  d_out may be d_in only for float
+ * input.  nplanes == 0 does nothing. */
+int sgpu_subsky_rbf_planes_device(sgpu_context *ctx, const void *d_in, int elem_size, int nplanes, int width,
+		int height, long plane_stride, int samples, double tolerance, double smooth, int divide, float *d_out,
+		float *d_med, unsigned char *d_keep, double *d_weights, double *d_mean, int *d_kept, int *d_status,
+		double *lam_rel_out);
+/* The solve alone: nsys systems [A | rhs] of one order (1 .. 1025), each
+ * order x (order + 1) doubles, row-major, overwritten; right-looking LU with
+ * partial pivoting (the largest |a|, the lowest row among equals, a NaN above
+ * everything) and a column-oriented back substitution, one workgroup per
+ * system.  d_x[nsys * order]; d_status: 0, or 2 for a pivot that is 0 or not
+ * finite, with x = +0. */
+int sgpu_bkg_rbf_solve_device(sgpu_context *ctx, int nsys, int order, double *d_aug, double *d_x, int *d_status);
+/* Kernel times of the last sgpu_subsky_rbf_planes_device call (HIP events on
+ * the context's stream; waits for the call): box medians, selection + system
+ * + solve, evaluation pass, the whole call. */
+int sgpu_bkg_rbf_last_kernel_ms(sgpu_context *ctx, float ms[4]);
+
 /* ---- a trous wavelets (the `wavelet` and `wrecons` commands) --------------- */
 
 /* Arithmetic: the specification in DESIGN.md 6j (W0-W5), restated in

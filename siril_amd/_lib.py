@@ -51,6 +51,7 @@ EXPORTS = (
     "sgpu_cosmetic_correction_device", "sgpu_dark_optimize_device", "sgpu_calibrate_frames_device",
     "sgpu_bkg_default_params", "sgpu_bkg_grid", "sgpu_subsky_planes_device",
     "sgpu_bkg_last_kernel_ms",
+    "sgpu_bkg_rbf_check", "sgpu_subsky_rbf_planes_device", "sgpu_bkg_rbf_solve_device", "sgpu_bkg_rbf_last_kernel_ms",
     "sgpu_wavelet_check", "sgpu_wavelet_planes_device", "sgpu_wavelet_reconstruct_device",
     "sgpu_wrecons_planes_device", "sgpu_wavelet_last_kernel_ms",
     "sgpu_star_default_params", "sgpu_match_default_params", "sgpu_star_smooth_table", "sgpu_find_stars_device",
@@ -399,6 +400,15 @@ def lib():
                                                 vp, vp]
         L.sgpu_bkg_last_kernel_ms.restype = i
         L.sgpu_bkg_last_kernel_ms.argtypes = [vp, C.POINTER(f)]
+        L.sgpu_bkg_rbf_check.restype = i
+        L.sgpu_bkg_rbf_check.argtypes = [i, i, i, C.c_double, C.c_double]
+        L.sgpu_subsky_rbf_planes_device.restype = i
+        L.sgpu_subsky_rbf_planes_device.argtypes = [vp, vp, i, i, i, i, C.c_long, i, C.c_double, C.c_double, i, vp, vp,
+                                                    vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
+        L.sgpu_bkg_rbf_solve_device.restype = i
+        L.sgpu_bkg_rbf_solve_device.argtypes = [vp, i, i, vp, vp, vp]
+        L.sgpu_bkg_rbf_last_kernel_ms.restype = i
+        L.sgpu_bkg_rbf_last_kernel_ms.argtypes = [vp, C.POINTER(f)]
         L.sgpu_wavelet_check.restype = i
         L.sgpu_wavelet_check.argtypes = [i, i, i, i]
         L.sgpu_wavelet_planes_device.restype = i

@@ -25,6 +25,11 @@ background extraction of every frame (siril_amd/background.py), degree 1 .. 4, e
 <prefix><name>NNNNN.fit and the new .seq.  -nodither is accepted (the output is float, nothing is dithered); -rbf and
 -smooth= are refused.
 
+`python -m siril_amd.cli subsky <image> {-rbf | <degree>} [-samples=20] [-tolerance=1.0] [-smooth=0.5] [-nodither]
+[-divide] [-out=FILE]`: background extraction of one image, each layer on its own: the polynomial of the given degree,
+or with -rbf a thin-plate spline through the kept sample boxes, evaluated at every pixel; writes one 32-bit image,
+<stem>_subsky.fit unless -out= names it.  -smooth= belongs to -rbf; -dither is refused.
+
 `python -m siril_amd.cli wavelet <image> <nbr_layers> <type> [-prefix=]`: the a trous wavelet planes of an image
 (siril_amd/wavelets.py), type 1 linear or 2 B3 spline; writes the nbr_layers planes (the details, then the residual)
 as 32-bit <prefix><stem>_wavelet<k>.fit.  `python -m siril_amd.cli wrecons <image> c1 ... cn [-type=1|2] [-out=FILE]`
@@ -49,6 +54,13 @@ def main(argv=None):
         out, info = run_seqsubsky(argv)
         print(f"Background extracted to {out} in {time.perf_counter() - t0:.3f} s; sample boxes kept per plane "
               f"{int(info['kept'].min())} .. {int(info['kept'].max())}")
+        return 0
+    if argv and argv[0] == "subsky":
+        from siril_amd.background import run_subsky
+        t0 = time.perf_counter()
+        out, info = run_subsky(argv)
+        print(f"Background extracted to {out} in {time.perf_counter() - t0:.3f} s; sample boxes kept per layer "
+              + " ".join(str(int(v)) for v in info["kept"].ravel()))
         return 0
     if argv and argv[0] == "wavelet":
         from siril_amd.wavelets import run_wavelet

@@ -16,7 +16,8 @@
 //                      bit by bit from the top, each bit from ten ballots
 //   k_bkg_fit          one workgroup per plane: the medians of the K box
 //                      medians and of their deviations by rank counting in
-//                      LDS, the keep mask, the 120 + 15 normal sums one per
+//                      LDS and the keep mask (bkg_kernels.h, shared with the
+//                      spline model), the 120 + 15 normal sums one per
 //                      thread (each walks the boxes in ascending k), Cholesky
 //                      and the mean in thread 0; the axis moments of the mean
 //                      depend on W and H alone and come from the host
@@ -32,6 +33,7 @@
 #include <cstdint>
 
 #include "bkg_host.h"
+#include "bkg_kernels.h"
 #include "sgpu_internal.h"
 
 #pragma clang fp contract(off)
@@ -44,7 +46,6 @@ namespace sgpu {
 typedef float bvf4 __attribute__((ext_vector_type(4)));      // nontemporal builtins take clang vectors
 
 constexpr int BKG_SLOTS = (BKG_NS + 63) / 64;       // 10
-constexpr int BKG_FIT_THREADS = 1024;
 
 // ---- B2 -----------------------------------------------------------------------
 template <typename T>
@@ -85,30 +86,6 @@ __global__ __launch_bounds__(256) void k_bkg_box_median(const T *in, long long p
 }
 
 // ---- B3 - B5 --------------------------------------------------------------------
-// The elements of ranks r0 and r1 of a[0 .. K) (ascending, ties by index) -> res[0], res[1]:
-// every thread counts, for each of its elements (one per 1024 boxes), the elements that sort before it.
-__device__ __forceinline__ void bkg_rank_select(const double *a, int K, int r0, int r1, double *res) {
-    for (int i = threadIdx.x; i < K; i += BKG_FIT_THREADS) {       // whole wavefronts without an element skip the walk
-        const double x = a[i];
-        int cnt = 0;
-        for (int j = 0; j < K; j++) {
-            const double v = a[j];      // one address for the wavefront: a broadcast
-            cnt += (int)(v < x) | ((int)(v == x) & (int)(j < i));
-        }
-        if (cnt == r0) res[0] = x;
-        if (cnt == r1) res[1] = x;
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ double bkg_lds_median(const double *a, int K, double *res) {
-    const bool odd = K & 1;
-    bkg_rank_select(a, K, odd ? K / 2 : K / 2 - 1, K / 2, res);
-    const double m = odd ? res[0] : (res[0] + res[1]) * 0.5;
-    __syncthreads();        // res and a are free again
-    return m;
-}
-
 // mom: B5's axis moments Mx[0 .. 4], My[0 .. 4].  They depend on the plane's size alone, so the
 // host computes them once per size (the same functions, the same bits) and keeps them on the device.
 
@@ -124,29 +101,9 @@ __global__ __launch_bounds__(BKG_FIT_THREADS) void k_bkg_fit(const float *med_al
     __shared__ double s_res[2], s_A[BKG_NCOEF * BKG_NCOEF], s_g[BKG_NCOEF], s_L[BKG_NCOEF * BKG_NCOEF], s_y[BKG_NCOEF],
         s_c[BKG_NCOEF];
     __shared__ int s_kept;
-    const float *med = med_all + (size_t)plane * K;
-    if (tid == 0) s_kept = 0;
-    for (int k = tid; k < K; k += BKG_FIT_THREADS) {
-        const float m = med[k];
-        s_med[k] = m;
-        s_d[k] = (double)m;
-    }
-    __syncthreads();
-    const double m = bkg_lds_median(s_d, K, s_res);
-    for (int k = tid; k < K; k += BKG_FIT_THREADS) s_d[k] = fabs((double)s_med[k] - m);
-    __syncthreads();
-    const double mad = bkg_lds_median(s_d, K, s_res);
-    const double T = m + tol * mad;
-    int mine = 0;
-    for (int k = tid; k < K; k += BKG_FIT_THREADS) {
-        const uint8_t kp = bkg_keep(s_med[k], T) ? 1 : 0;
-        s_keep[k] = kp;
-        keep_all[(size_t)plane * K + k] = kp;
-        mine += kp;
-    }
-    if (mine) atomicAdd(&s_kept, mine);
-    __syncthreads();
-    const int kept = s_kept, n = bkg_ncoef(degree);
+    const int kept = bkg_select_lds(med_all + (size_t)plane * K, K, tol, s_d, s_med, s_keep, s_res, &s_kept,
+                                    keep_all + (size_t)plane * K);
+    const int n = bkg_ncoef(degree);
     int st = kept < n ? 1 : 0;
     if (!st) {
         if (tid < BKG_NPAIR) {
@@ -275,6 +232,20 @@ __global__ __launch_bounds__(256) void k_bkg_apply_scalar(const T *in, float *ou
 }  // namespace sgpu
 
 // ===================================================================== host
+// the spline model's way to k_bkg_box_median (background_rbf.hip)
+int sgpu::bkg_launch_box_median(sgpu_context *c, const void *d_in, int elem_size, long long pstride, int W,
+                                const BkgGrid &g, long long nbox, float *d_med) {
+    const dim3 grid((unsigned)((nbox + 3) / 4));
+    if (elem_size == 4)
+        hipLaunchKernelGGL((sgpu::k_bkg_box_median<float>), grid, dim3(256), 0, c->stream, (const float *)d_in, pstride,
+                           W, g, nbox, d_med);
+    else
+        hipLaunchKernelGGL((sgpu::k_bkg_box_median<uint16_t>), grid, dim3(256), 0, c->stream, (const uint16_t *)d_in,
+                           pstride, W, g, nbox, d_med);
+    HIP_TRY(hipGetLastError());
+    return SGPU_OK;
+}
+
 namespace {
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }

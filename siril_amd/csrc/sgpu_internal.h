@@ -157,6 +157,10 @@ struct sgpu_context {
     double bkg_M[10] = {};                                 // axis moments Mx[0 .. 4], My[0 .. 4] of bkg_M_key's size
     int bkg_M_key[2] = {0, 0};
     int bkg_timed = 0;                                     // the events of a call are recorded
+    // thin-plate-spline background: [A | rhs] of the planes of one launch, the samples' coordinates, result arrays
+    sgpu_host::DevBuf rbf_ws, rbf_res;
+    hipEvent_t rbf_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // box medians start, fit start, evaluation start, stop
+    int rbf_timed = 0;
     // wavelets: c_j ping-pong and the row-pass result, three float planes per input plane
     sgpu_host::DevBuf wav_ws;
     hipEvent_t wav_ev[17] = {};                            // one before every launch of a call, one after the last
@@ -170,7 +174,7 @@ struct sgpu_context {
                                      &dft_frames, &rl_u, &rl_e, &rl_f, &rl_r, &rl_w, &rl_taps, &rl_small,
                                      &rl_io, &rl_reg, &rl_gxy, &rlf_t1, &rlf_t2, &rlf_ka, &rlf_kb, &rlf_kt, &rlf_tw1, &rlf_tw2, &dm_ws, &dm_mm, &dm_io, &ns_state, &ns_hist, &ns_part, &ns_io, &bn_rows, &qe_buf, &qe_part, &qe_io, &onorm, &ov_ws, &ov_tab,
                                      &fb2_list, &fb2_count, &wz_ws, &wz_cnt, &fe_tab, &fe_dt, &cfa_tmp, &cstripe, &warp_ws, &drz_ws, &cal_rows, &cal_k, &cal_cnt, &cal_plan,
-                                     &star_tc, &star_slots, &star_fp, &star_out, &psf_jobs, &psf_out, &bkg_ws, &bkg_mom, &wav_ws,
+                                     &star_tc, &star_slots, &star_fp, &star_out, &psf_jobs, &psf_out, &bkg_ws, &bkg_mom, &rbf_ws, &rbf_res, &wav_ws,
                                      &seq_in[0], &seq_in[1], &seq_out, &seq_lo, &seq_hi, &seq_cnt})
             b->release();
         seq_pin[0].release();
