@@ -426,6 +426,47 @@ double sgpu_rl_last_iter_flops(sgpu_context *ctx);
 long sgpu_rl_last_fft_convs(sgpu_context *ctx);
 double sgpu_rl_last_iter_bytes(sgpu_context *ctx);
 
+/* The Richardson-Lucy kernels alone (tests).
+ *
+ * sgpu_rl_conv_device: one convolution plus point-wise step (epilogue) of a
+ * device-resident W x H float image, d_out[y][x] = epi(c[y][x]) with
+ *   c[y][x] = sum_{ky,kx} taps[ky][kx] * in[y + ks/2 - ky][x + ks/2 - kx]
+ * (a convolution; indices modulo H, W when wrap = 1, zero outside when
+ * wrap = 0).  `taps` is a ks x ks HOST array used as it stands: no
+ * normalisation, no flip.
+ *   path  0: the direct matrix-core kernel; 1: the FFT convolution
+ *   epi   0 store c; 1 f / sanitize(c); 2 max(1e-9, f / c); 3 c * est;
+ *         4 est + dt (-1 + c); 5 w in + (1 - w) c with w = wy[y] wx[x];
+ *         6 c est / (1 - rlam w); 7 est + dt ((-1 + rlam w) + c)
+ *   d_f, d_est, d_w, d_wy, d_wx   the operands the epilogue reads (others may
+ *         be NULL); d_est may alias d_out
+ *   stop_out  optional host double: sum |new - ref| / |ref| of epilogues 3, 4,
+ *         6, 7, ref = d_stop_ref or (NULL) the old estimate; 0 for the others
+ *   chain (path 1 only; -1 for path 0) -1: standalone; else bit 0: the work
+ *         plane holds the spectrum of d_in, left by the previous call on this
+ *         context; bit 1: leave the spectrum of d_out for the next call
+ * Domain, checked before anything is launched (SGPU_BAD_ARGUMENT): ks odd and
+ * <= sgpu_rl_max_conv_ks(); W, H >= 1; d_out does not overlap d_in; the
+ * epilogue's operands non-NULL; wrap = 1 needs min(W, H) >= ks/2 + 1; path 1
+ * needs wrap = 1 and sgpu_rl_fft_smooth_len(W + 3 (ks/2)), (H + 3 (ks/2)) both
+ * non-zero; chain bit 0 needs the previous call on the context to have left a
+ * spectrum (chain bit 1) for the same W, H, ks.  Returns after the stream has
+ * been synchronised.
+ *
+ * sgpu_rl_reg_device: the regulariser weight of one iteration from the
+ * estimate d_e into d_w (mode 0 FFT-path TV, 1 FFT-path FH, 2 naive TV,
+ * 3 naive FH, which also stores gxy into d_gxy when non-NULL); W, H >= 2,
+ * outputs must not overlap the input.  Synchronises the stream. */
+int sgpu_rl_conv_device(sgpu_context *ctx, int path, int wrap, int epi, const float *d_in, float *d_out, int W, int H,
+		const float *taps, int ks, const float *d_f, const float *d_est, const float *d_w,
+		const float *d_stop_ref, const float *d_wy, const float *d_wx, float dt, float rlam, double *stop_out,
+		int chain);
+int sgpu_rl_reg_device(sgpu_context *ctx, const float *d_e, float *d_w, float *d_gxy, int W, int H, int mode);
+/* Largest PSF size of the direct kernel (its tile + taps fit 160 KiB of LDS);
+ * smallest even 2-3-5-smooth FFT length >= need, 0 when none is <= 8192. */
+int sgpu_rl_max_conv_ks(void);
+int sgpu_rl_fft_smooth_len(int need);
+
 /* CFA sequences (nb_layers == 1): register_shift_dft first runs
  * interpolate_nongreen on each selection (shift_methods.c:115-117,214-215;
  * io/image_format_fits.c:4319-4349).  Same as above with the compiled CFA

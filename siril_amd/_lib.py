@@ -40,6 +40,7 @@ EXPORTS = (
     "sgpu_stack_seq_ex2", "sgpu_fits_layers", "sgpu_image_read_rows", "sgpu_fits_write_planes", "sgpu_ser_write",
     "sgpu_ser_info", "sgpu_overlap_rect", "sgpu_overlap_stats_device", "sgpu_overlap_stats_u16_device",
     "sgpu_overlap_factors", "sgpu_rl_last_fft_convs", "sgpu_rl_last_iter_bytes",
+    "sgpu_rl_conv_device", "sgpu_rl_reg_device", "sgpu_rl_max_conv_ks", "sgpu_rl_fft_smooth_len",
     "sgpu_stack_rows_planes", "sgpu_stack_rows_planes_device", "sgpu_stack_rows_u16_planes_device",
     "sgpu_set_input_bitpix", "sgpu_stack_seq_opts", "sgpu_stack_seq_frames",
     "sgpu_stack_blocks", "sgpu_feather_mask_size", "sgpu_feather_masks_device", "sgpu_feather_block_area",
@@ -461,6 +462,15 @@ def lib():
         L.sgpu_rl_last_fft_convs.argtypes = [vp]
         L.sgpu_rl_last_iter_bytes.restype = C.c_double
         L.sgpu_rl_last_iter_bytes.argtypes = [vp]
+        L.sgpu_rl_conv_device.restype = i
+        L.sgpu_rl_conv_device.argtypes = [vp, i, i, i, vp, vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, f, f,
+                                          C.POINTER(C.c_double), i]
+        L.sgpu_rl_reg_device.restype = i
+        L.sgpu_rl_reg_device.argtypes = [vp, vp, vp, vp, i, i, i]
+        L.sgpu_rl_max_conv_ks.restype = i
+        L.sgpu_rl_max_conv_ks.argtypes = []
+        L.sgpu_rl_fft_smooth_len.restype = i
+        L.sgpu_rl_fft_smooth_len.argtypes = [i]
         _lib = L
     return _lib
 

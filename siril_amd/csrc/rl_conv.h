@@ -26,6 +26,15 @@ enum Reg : int {
     REG_W_NAIVE_FH = 3,   // img_t path: max(1e-9, g)^2 terms; also stores gxy
 };
 
+// Domain of the direct kernel (launch_conv): ks odd, <= max_conv_ks(); W, H >= 1.
+// With wrap = 1 also min(W, H) >= ks/2 + 1 (check_args and the slice plan
+// guarantee it; sgpu_rl_conv_device refuses anything else).  The kernel reads
+// `in` only at wrapped coordinates of cells whose unwrapped coordinate lies in
+// [-h, n + h), h = ks/2, n the extent: there -2n <= v < 3n holds because
+// h <= 2n, so its two-step wrap is an exact modulo and every read stays inside
+// the W x H input.  The rest of a 64 x 64 tile's halo (it always reaches
+// 63 + h past the tile origin, beyond 3n on a small image) is filled with 0
+// without a load; it feeds only outputs outside the image, which are not stored.
 struct ConvArgs {
     const float *in;      // H x W input (the convolved image)
     float *out;           // H x W output; must not alias `in`

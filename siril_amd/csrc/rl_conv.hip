@@ -128,22 +128,36 @@ __global__ __launch_bounds__(256) void k_conv2d_mfma(ConvArgs a, int epi) {
     }
     if (threadIdx.x < GUARD) lds[threadIdx.x] = 0.f;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    // tile + halo: one wave per row, lanes along the row
+    // tile + halo: one wave per row, lanes along the row.  The tile spans
+    // [-hk, 63 + hk] from its origin whatever the image size; in wrap mode only
+    // the cells with an unwrapped coordinate in [-hk, n + hk) feed an output
+    // inside the image (ox < W, oy < H reach at most n - 1 + hk).  The others
+    // feed outputs the epilogue discards: they get 0 and issue no load, since
+    // the double wrapi is a modulo only on [-2n, 3n) and would index past the
+    // input on a small image (ConvArgs, rl_conv.h).  X0, Y0 >= 0, so only the
+    // upper end can leave the range: cells [0, cend) of a row are loaded.  A
+    // row that lies inside whole (every row of a tile away from the right and
+    // bottom edges) runs the unpredicated loop.
+    const int cwrap = min(TW, W + 2 * hk - X0);
     for (int r = wave; r < TH; r += 4) {
         int y = Y0 - hk + r;
-        bool yin = true;
-        if (a.wrap) y = wrapi(wrapi(y, H), H);
-        else yin = (y >= 0 && y < H);
-        const float *row = a.in + (long long)(yin ? y : 0) * W;
-        for (int c = lane; c < TW; c += 64) {
-            int x = X0 - hk + c;
-            float v;
-            if (a.wrap) {
-                v = row[wrapi(wrapi(x, W), W)];
+        float *trow = tile + r * TW;
+        if (a.wrap) {
+            const int cend = (y < H + hk) ? cwrap : 0;           // wave-uniform
+            const float *row = a.in + (long long)(cend ? wrapi(wrapi(y, H), H) : 0) * W;
+            if (cend == TW) {
+                for (int c = lane; c < TW; c += 64) trow[c] = row[wrapi(wrapi(X0 - hk + c, W), W)];
             } else {
-                v = (yin && x >= 0 && x < W) ? row[x] : 0.f;
+                for (int c = lane; c < TW; c += 64)
+                    trow[c] = (c < cend) ? row[wrapi(wrapi(X0 - hk + c, W), W)] : 0.f;
             }
-            tile[r * TW + c] = v;
+        } else {
+            const bool yin = (y >= 0 && y < H);
+            const float *row = a.in + (long long)(yin ? y : 0) * W;
+            for (int c = lane; c < TW; c += 64) {
+                const int x = X0 - hk + c;
+                trow[c] = (yin && x >= 0 && x < W) ? row[x] : 0.f;
+            }
         }
     }
     __syncthreads();

@@ -184,7 +184,7 @@ __global__ __launch_bounds__(fft::kThreads) void k_rlf_rows_inv(Plan pl, HPlane 
 
 // k_rlf_rows_inv followed, in the same block, by the forward transform of
 // the two output rows as rows of the next convolution's periodic extension
-// (ext row y + h, plus its wrap copy y + h + H for y < h or y + h - H for
+// (ext row y + h, plus its wrap copies y + h + H for y < h and y + h - H for
 // y >= H - h), written back into t1.  The rows the block reads (h + y0,
 // h + y1) are the ones it rewrites; wrap copies land outside [h, h + H), which
 // no block reads.  Rows >= H + 2h are zeroed by the host.
@@ -236,17 +236,22 @@ __global__ __launch_bounds__(fft::kThreads) void k_rlf_rows_inv_fwd(Plan pl, HPl
     __syncthreads();
     const float2 *f = fft::run<-1>(a, b, pl);
     const int ry0 = y0 + h, ry1 = y1 + h;
-    const int wy0 = y0 < h ? y0 + h + H : (y0 >= H - h ? y0 + h - H : -1);
-    const int wy1 = !has1 ? -1 : (y1 < h ? y1 + h + H : (y1 >= H - h ? y1 + h - H : -1));
+    // wrap copies: past the window's end for y < h (lo), ahead of its start for
+    // y >= H - h (hi) -- both when H < 2h (two independent conditions, as for
+    // the columns above)
+    const int lo0 = y0 < h ? y0 + h + H : -1, hi0 = y0 >= H - h ? y0 + h - H : -1;
+    const int lo1 = (has1 && y1 < h) ? y1 + h + H : -1, hi1 = (has1 && y1 >= H - h) ? y1 + h - H : -1;
     for (int k = threadIdx.x; k < nh; k += blockDim.x) {
         const float2 z = f[k], zc = f[k == 0 ? 0 : n - k];
         const float2 X = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y));
         const float2 Y = make_float2(0.5f * (z.y + zc.y), 0.5f * (zc.x - z.x));
         t.p[t.at(ry0, k)] = X;
-        if (wy0 >= 0) t.p[t.at(wy0, k)] = X;
+        if (lo0 >= 0) t.p[t.at(lo0, k)] = X;
+        if (hi0 >= 0) t.p[t.at(hi0, k)] = X;
         if (has1) {
             t.p[t.at(ry1, k)] = Y;
-            if (wy1 >= 0) t.p[t.at(wy1, k)] = Y;
+            if (lo1 >= 0) t.p[t.at(lo1, k)] = Y;
+            if (hi1 >= 0) t.p[t.at(hi1, k)] = Y;
         }
     }
     if (ca.stop_acc) {
@@ -357,9 +362,20 @@ int fft_conv_chain(const FftConv &fc, const ConvArgs &a, const float2 *khat, int
                    hipStream_t s) {
     if (a.W != fc.W || a.H != fc.H || a.ks / 2 != fc.h) return -1;
     const Plan p1 = make_plan(fc.n1, fc.tw1), p2 = make_plan(fc.n2, fc.tw2);
+    // The fused inverse + forward row kernel packs IMAGE rows 2j, 2j + 1 into
+    // one complex transform; the standalone forward pass packs rows 2j, 2j + 1
+    // of the periodic EXTENSION, image rows 2j - h, 2j + 1 - h.  A row's
+    // spectrum, separated from the packed transform, depends in its last bits
+    // on its partner, so the fused kernel leaves the bits a standalone
+    // convolution would compute only when h is even and -- for the wrap copies
+    // and the last row, which is single at odd H -- H is even.  At any other
+    // parity the output's spectrum is left by the plain inverse pass followed
+    // by the forward pass on the output: the chain then saves nothing, and
+    // stays bit-identical.
+    const bool fused = next && fc.h % 2 == 0 && fc.H % 2 == 0;
     // the in-place kernels keep their outputs in registers per thread: plans
     // with a generic radix (never chosen: 2-3-5-smooth lengths) are refused
-    if (next && !fft::plan_inplace(p1)) return -1;
+    if (fused && !fft::plan_inplace(p1)) return -1;
     // the chain keeps the next input's spectra where the row kernels left
     // them: t1 (row-major, transpose kernels) or t2 (column-major, default)
     const bool tk = rl_transpose_kernel();
@@ -377,7 +393,7 @@ int fft_conv_chain(const FftConv &fc, const ConvArgs &a, const float2 *khat, int
     if (tk)
         hipLaunchKernelGGL(dft::k_transpose_rect, dim3((fc.n2 + 31) / 32, (fc.nh1 + 31) / 32, 1), dim3(256), 0, s,
                            fc.t2, fc.t1, fc.nh1, fc.n2);
-    if (next) {
+    if (fused) {
         hipLaunchKernelGGL(k_rlf_rows_inv_fwd, dim3((fc.H + 1) / 2), dim3(fft::kThreads), fft::plan_lds_bytes(p1), s,
                            p1, rows, fc.h, a, epi);
         const int l2 = fc.H + 2 * fc.h;      // rows of the extension; the rest must read as zero
@@ -394,6 +410,11 @@ int fft_conv_chain(const FftConv &fc, const ConvArgs &a, const float2 *khat, int
     } else {
         hipLaunchKernelGGL(k_rlf_rows_inv, dim3((fc.H + 1) / 2), dim3(fft::kThreads), fft::plan_lds_bytes(p1), s,
                            p1, rows, fc.h, a, epi);
+        if (next) {
+            SrcDesc d{a.out, fc.W, fc.H, fc.h, a.ks, 0, fc.n1, fc.n2};
+            hipLaunchKernelGGL(k_rlf_rows_fwd, dim3((fc.n2 + 1) / 2), dim3(fft::kThreads), fft::plan_lds_bytes(p1),
+                               s, p1, d, rows);
+        }
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -108,6 +108,8 @@ struct sgpu_context {
     // Richardson-Lucy FFT convolution: work planes, taps spectra, twiddles
     sgpu_host::DevBuf rlf_t1, rlf_t2, rlf_ka, rlf_kb, rlf_kt, rlf_tw1, rlf_tw2;
     int rlf_n1 = 0, rlf_n2 = 0;           // lengths the twiddle tables hold
+    int rlf_spec_w = 0, rlf_spec_h = 0, rlf_spec_ks = 0;   // sgpu_rl_conv_device: geometry of the spectrum its
+                                                           // last call left in the work plane (0: none)
     long rl_fft_convs = 0;                // FFT convolutions of the last call
     double rl_iter_bytes = 0.0;           // algorithmic HBM bytes of the iteration convolutions
     size_t rl_memory = (size_t)1 << 40;   // slicing budget (get_available_memory() in the reference)

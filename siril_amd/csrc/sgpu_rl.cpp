@@ -216,10 +216,10 @@ int upload_twiddles(sgpu_context *c, sgpu_host::DevBuf &buf, int n) {
 // FFT-convolution plan of a W x H slice with a ks x ks kernel, or fc.n1 = 0
 // when the direct convolution is used (SGPU_RL_DIRECT=1, or no smooth
 // length <= 8192 covers the extended slice)
-int fft_plan(sgpu_context *c, int W, int H, int ks, sgpu::rl::FftConv &fc) {
+int fft_plan(sgpu_context *c, int W, int H, int ks, sgpu::rl::FftConv &fc, bool knob = true) {
     fc.n1 = 0;
     const char *ev = std::getenv("SGPU_RL_DIRECT");
-    if (ev && ev[0] == '1') return SGPU_OK;
+    if (knob && ev && ev[0] == '1') return SGPU_OK;
     const int h = ks / 2;
     const int n1 = sgpu::rl::fft_smooth_len(W + 3 * h), n2 = sgpu::rl::fft_smooth_len(H + 3 * h);
     if (!n1 || !n2) return SGPU_OK;
@@ -395,7 +395,9 @@ int rl_channel(sgpu_context *c, const float *d_f, float *d_u, int rx, int ry, st
         // zero-initialised image and the measure never fires
         const bool use_stop = ra.stop_active == 1 && (!ra.naive || Gxy);
         // SGPU_RL_CHAIN=1: chain the spectra through the iteration (fused
-        // inverse + forward row pass; bit-identical, measured slower: the
+        // inverse + forward row pass where ks/2 and the slice height are even,
+        // the two plain passes elsewhere: fft_conv_chain; bit-identical,
+        // measured slower: the
         // fused kernel's registers halve its occupancy, 195 us against
         // 91 + 51 us for the two passes) -- A/B knob, off by default
         const char *cev = std::getenv("SGPU_RL_CHAIN");
@@ -474,6 +476,7 @@ int rl_device(sgpu_context *c, float *d_fdata, unsigned rx, unsigned ry, unsigne
     c->rl_iter_flops = 0.0;
     c->rl_iter_bytes = 0.0;
     c->rl_fft_convs = 0;
+    c->rlf_spec_w = c->rlf_spec_h = c->rlf_spec_ks = 0;   // the work planes are reused below
     for (unsigned ch = 0; ch < nchans; ch++) {
         const unsigned kc = ch < kchans ? ch : 0;
         std::vector<float> K(kernel + (size_t)kc * ks * ks, kernel + (size_t)(kc + 1) * ks * ks);
@@ -573,6 +576,108 @@ extern "C" int sgpu_naive_richardson_lucy(float *fdata, unsigned rx, unsigned ry
     return sgpu_rl_naive(c, fdata, rx, ry, nchans, kernel, kernelsize, kchans, lambda, maxiter, stopcriterion,
                          regtype, stepsize, stopcriterion_active);
 }
+
+// ---- the kernels alone (tests): one convolution + epilogue, one regulariser pass
+
+namespace {
+
+bool overlaps(const void *a, const void *b, size_t bytes) {
+    const char *p = (const char *)a, *q = (const char *)b;
+    return p < q + bytes && q < p + bytes;
+}
+
+}  // namespace
+
+extern "C" int sgpu_rl_conv_device(sgpu_context *c, int path, int wrap, int epi, const float *d_in, float *d_out,
+                                   int W, int H, const float *taps, int ks, const float *d_f, const float *d_est,
+                                   const float *d_w, const float *d_stop_ref, const float *d_wy, const float *d_wx,
+                                   float dt, float rlam, double *stop_out, int chain) {
+    namespace R = sgpu::rl;
+    if (!c || !d_in || !d_out || !taps) return fail(SGPU_BAD_ARGUMENT, "null argument");
+    // whatever this call does, the spectrum a previous call left is spent
+    const bool spec_ok = c->rlf_spec_w == W && c->rlf_spec_h == H && c->rlf_spec_ks == ks && W > 0;
+    c->rlf_spec_w = c->rlf_spec_h = c->rlf_spec_ks = 0;
+    if ((path != 0 && path != 1) || (wrap != 0 && wrap != 1) || epi < R::EPI_STORE || epi > R::EPI_GRAD_REG)
+        return fail(SGPU_BAD_ARGUMENT, "unknown path, wrap or epilogue");
+    if (ks < 1 || !(ks & 1) || ks > R::max_conv_ks()) return fail(SGPU_BAD_ARGUMENT, "PSF size must be odd and <= max_conv_ks");
+    if (W < 1 || H < 1) return fail(SGPU_BAD_ARGUMENT, "empty image");
+    const size_t bytes = (size_t)W * H * sizeof(float);
+    if (overlaps(d_in, d_out, bytes)) return fail(SGPU_BAD_ARGUMENT, "out aliases in");
+    const bool upd = epi == R::EPI_MULT || epi == R::EPI_GRAD || epi == R::EPI_MULT_REG || epi == R::EPI_GRAD_REG;
+    if (((epi == R::EPI_RATIO || epi == R::EPI_RATIO_NAIVE) && !d_f) || (upd && !d_est) ||
+        ((epi == R::EPI_MULT_REG || epi == R::EPI_GRAD_REG) && !d_w) || (epi == R::EPI_TAPER && (!d_wy || !d_wx)))
+        return fail(SGPU_BAD_ARGUMENT, "the epilogue's operand is null");
+    const int h = ks / 2;
+    if (wrap && std::min(W, H) < h + 1) return fail(SGPU_BAD_ARGUMENT, "circular convolution needs min(W, H) >= ks/2 + 1");
+    if (path == 0) {
+        if (chain != -1) return fail(SGPU_BAD_ARGUMENT, "the direct path has no spectrum chain");
+    } else {
+        if (!wrap) return fail(SGPU_BAD_ARGUMENT, "the FFT path is circular");
+        if (chain < -1 || chain > 3) return fail(SGPU_BAD_ARGUMENT, "unknown chain flags");
+        if ((long long)W + 3 * h > 8192 || (long long)H + 3 * h > 8192 || !R::fft_smooth_len(W + 3 * h) ||
+            !R::fft_smooth_len(H + 3 * h))
+            return fail(SGPU_BAD_ARGUMENT, "no FFT length <= 8192 covers the extended image");
+        if (chain >= 0 && (chain & 1) && !spec_ok)
+            return fail(SGPU_BAD_ARGUMENT, "no spectrum of this geometry left by the previous call");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int r;
+    if ((r = c->rl_taps.ensure((size_t)3 * ks * ks * 4)) || (r = c->rl_small.ensure(256))) return r;
+    float *d_taps = (float *)c->rl_taps.p;
+    HIP_TRY(hipMemcpyAsync(d_taps, taps, (size_t)ks * ks * 4, hipMemcpyHostToDevice, s));
+    double *stop = nullptr;
+    if (stop_out && upd) {
+        stop = (double *)((char *)c->rl_small.p + 64);
+        HIP_TRY(hipMemsetAsync(stop, 0, sizeof(double), s));
+    }
+    if (path == 0) {
+        r = conv(c, d_in, d_out, W, H, d_taps, ks, wrap, epi, d_f, d_est, dt, d_wy, d_wx, stop, d_w, rlam, d_stop_ref);
+    } else {
+        R::FftConv fc;
+        if ((r = fft_plan(c, W, H, ks, fc, false))) return r;
+        if (!fc.n1) return fail(SGPU_BAD_ARGUMENT, "no FFT plan");
+        // the taps' spectrum stages through a plane of its own: t1 may hold
+        // the chained spectrum of the input
+        R::FftConv ft = fc;
+        ft.t1 = (float2 *)c->rlf_ka.p;
+        if (R::fft_conv_taps(ft, d_taps, ks, (float2 *)c->rlf_kt.p, s))
+            return fail(SGPU_NO_DEVICE, "taps spectrum launch failed");
+        r = fconv(c, fc, (const float2 *)c->rlf_kt.p, d_in, d_out, W, H, ks, epi, d_f, d_est, dt, d_wy, d_wx, stop, d_w,
+                  rlam, d_stop_ref, chain);
+    }
+    if (r) return r;
+    if (stop_out) {
+        *stop_out = 0.0;
+        if (stop) HIP_TRY(hipMemcpyAsync(stop_out, stop, sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (path == 1 && chain >= 0 && (chain & 2)) {
+        c->rlf_spec_w = W;
+        c->rlf_spec_h = H;
+        c->rlf_spec_ks = ks;
+    }
+    return SGPU_OK;
+}
+
+extern "C" int sgpu_rl_reg_device(sgpu_context *c, const float *d_e, float *d_w, float *d_gxy, int W, int H,
+                                  int mode) {
+    namespace R = sgpu::rl;
+    if (!c || !d_e || !d_w) return fail(SGPU_BAD_ARGUMENT, "null argument");
+    if (mode < R::REG_W_FFT_TV || mode > R::REG_W_NAIVE_FH) return fail(SGPU_BAD_ARGUMENT, "unknown regulariser mode");
+    if (W < 2 || H < 2 || (long long)W * H > 0x7fffffffLL) return fail(SGPU_BAD_ARGUMENT, "image must be at least 2 x 2");
+    const size_t bytes = (size_t)W * H * sizeof(float);
+    if (overlaps(d_e, d_w, bytes) || (d_gxy && (overlaps(d_e, d_gxy, bytes) || overlaps(d_w, d_gxy, bytes))))
+        return fail(SGPU_BAD_ARGUMENT, "outputs alias the input");
+    HIP_TRY(hipSetDevice(c->device));
+    if (R::launch_reg(d_e, d_w, mode == R::REG_W_NAIVE_FH ? d_gxy : nullptr, W, H, mode, c->stream))
+        return fail(SGPU_NO_DEVICE, "regulariser launch failed");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SGPU_OK;
+}
+
+extern "C" int sgpu_rl_max_conv_ks(void) { return sgpu::rl::max_conv_ks(); }
+extern "C" int sgpu_rl_fft_smooth_len(int need) { return need > 0 ? sgpu::rl::fft_smooth_len(need) : 0; }
 
 extern "C" long sgpu_rl_last_conv_launches(sgpu_context *c) { return c ? c->rl_conv_launches : -1; }
 

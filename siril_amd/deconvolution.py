@@ -129,6 +129,71 @@ def set_memory_budget(nbytes: int, ctx=None) -> None:
     check(lib().sgpu_rl_set_memory(ctx.h, int(nbytes)), "sgpu_rl_set_memory")
 
 
+# ---- the kernels alone (sgpu_rl_conv_device / sgpu_rl_reg_device, include/sirilgpu.h)
+EPI_STORE, EPI_RATIO, EPI_RATIO_NAIVE, EPI_MULT, EPI_GRAD, EPI_TAPER, EPI_MULT_REG, EPI_GRAD_REG = range(8)
+REG_W_FFT_TV, REG_W_FFT_FH, REG_W_NAIVE_TV, REG_W_NAIVE_FH = range(4)
+PATH_DIRECT, PATH_FFT = 0, 1
+
+
+def _dev2d(t, name: str, shape=None):
+    import torch
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous float32 device tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}")
+    return C.c_void_p(t.data_ptr())
+
+
+def max_conv_ks() -> int:
+    return int(lib().sgpu_rl_max_conv_ks())
+
+
+def fft_smooth_len(need: int) -> int:
+    return int(lib().sgpu_rl_fft_smooth_len(int(need)))
+
+
+def rl_conv_device(x, taps, out, path: int = PATH_DIRECT, wrap: int = 1, epi: int = EPI_STORE, f=None, est=None,
+                   w=None, stop_ref=None, wy=None, wx=None, dt: float = 0.0, rlam: float = 0.0,
+                   want_stop: bool = False, chain: int = -1, ctx=None) -> Optional[float]:
+    """One convolution + epilogue of the (H, W) device tensor `x` into `out`
+    with the (ks, ks) host taps as they stand; returns the stop measure when
+    `want_stop`.  Raises SgpuError outside the entry point's domain."""
+    import torch
+    from .stacking import default_context
+    ctx = ctx or default_context()
+    k = np.ascontiguousarray(taps, np.float32)
+    if k.ndim != 2 or k.shape[0] != k.shape[1]:
+        raise ValueError("taps must be (ks, ks)")
+    if x.ndim != 2:
+        raise ValueError("x must be (H, W)")
+    H, W = x.shape
+    ctx.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+    stop = C.c_double(0.0)
+    check(lib().sgpu_rl_conv_device(
+        ctx.h, int(path), int(wrap), int(epi), _dev2d(x, "x"), _dev2d(out, "out", (H, W)), W, H,
+        k.ctypes.data_as(C.c_void_p), k.shape[0], _dev2d(f, "f", (H, W)), _dev2d(est, "est", (H, W)),
+        _dev2d(w, "w", (H, W)), _dev2d(stop_ref, "stop_ref", (H, W)), _dev2d(wy, "wy", (H,)),
+        _dev2d(wx, "wx", (W,)), float(dt), float(rlam), C.byref(stop) if want_stop else None, int(chain)),
+        "sgpu_rl_conv_device")
+    return stop.value if want_stop else None
+
+
+def rl_reg_device(e, w, gxy=None, mode: int = REG_W_FFT_TV, ctx=None) -> None:
+    """Regulariser weight of the (H, W) device tensor `e` into `w` (and `gxy`
+    for REG_W_NAIVE_FH)."""
+    import torch
+    from .stacking import default_context
+    ctx = ctx or default_context()
+    if e.ndim != 2:
+        raise ValueError("e must be (H, W)")
+    H, W = e.shape
+    ctx.set_stream(torch.cuda.current_stream(e.device).cuda_stream)
+    check(lib().sgpu_rl_reg_device(ctx.h, _dev2d(e, "e"), _dev2d(w, "w", (H, W)), _dev2d(gxy, "gxy", (H, W)), W, H,
+                                   int(mode)), "sgpu_rl_reg_device")
+
+
 def moffat_psf(ks: int, fwhm: float = 4.0, beta: float = 4.5, ellipticity: float = 1.0, angle: float = 0.0,
                offset=(0.0, 0.0)) -> np.ndarray:
     """Synthetic (optionally elliptical, off-centre) Moffat PSF, ks x ks float32."""
