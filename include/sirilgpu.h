@@ -797,6 +797,46 @@ int sgpu_wrecons_planes_device(sgpu_context *ctx, const void *d_in, int elem_siz
  * 3: reconstruction of stored planes.  Arrays of SGPU_WAVELET_MAX_LAUNCHES. */
 int sgpu_wavelet_last_kernel_ms(sgpu_context *ctx, float *ms, int *what, int *nlaunches);
 
+/* ---- median filter (the `fmedian` command) -------------------------------- */
+
+/* The specification is DESIGN.md 6l (M0-M5), restated in tests/median_ref.py;
+ * parity with a Siril binary is unpinned.  A plane is width x height samples
+ * (elem_size 2: WORD, scaled by 1/65535; 4: float).  The window is ksize x
+ * ksize, ksize odd in 3 .. 15, its taps reflected at the plane's edges as the
+ * wavelets' are; samples are ordered by their keys (-NaN < -inf < ... < -0 <
+ * +0 < ... < +inf < +NaN) and the median is the sample of rank (ksize^2 - 1)/2,
+ * returned with its own bits.  out = m when modulation is 1, otherwise
+ * modulation*m + (1 - modulation)*x in float, each operation rounded once.
+ * iterations 1 .. 8 repeat the filter on its own result; the planes in between
+ * live in the context's workspace (two float planes per input plane).  The
+ * call is asynchronous on the context's stream and copies nothing to the host.
+ * nplanes == 0 does nothing. */
+#define SGPU_FMEDIAN_MAX_LAUNCHES 8
+/* route: which kernel runs.  0 is the only value an application needs; the
+ * others exist so that the two routes can be compared bit for bit and timed
+ * against each other. */
+#define SGPU_FMEDIAN_ROUTE_AUTO 0        /* by ksize: the network up to SGPU_FMEDIAN_MAX_NETWORK_KSIZE, else the selection */
+#define SGPU_FMEDIAN_ROUTE_NETWORK 1     /* sorted columns and a selection network; SGPU_BAD_ARGUMENT for a ksize that has none */
+#define SGPU_FMEDIAN_ROUTE_SELECT 2      /* bisection over the key bits in which the window's extremes differ; every ksize */
+#define SGPU_FMEDIAN_ROUTE_SELECT_WIDE 3 /* the same over all 32 bits (measurements of what the narrowing gains) */
+#define SGPU_FMEDIAN_MAX_NETWORK_KSIZE 7
+/* SGPU_OK, or SGPU_BAD_ARGUMENT: ksize even or outside 3 .. 15, (ksize - 1)/2
+ * above min(width, height) - 1, modulation not finite or outside [0, 1],
+ * iterations outside 1 .. 8, a side above 65535.  Host only. */
+int sgpu_fmedian_check(int width, int height, int ksize, float modulation, int iterations);
+/* Plane p at d_in + p*plane_stride samples, its result at d_out + p*out_stride
+ * floats.  Also SGPU_BAD_ARGUMENT: elem_size other than 2 or 4, a stride below
+ * width*height, an output range that overlaps the input range, a route outside
+ * 0 .. 3. */
+int sgpu_fmedian_planes_device(sgpu_context *ctx, const void *d_in, int elem_size, int nplanes, int width, int height,
+		long plane_stride, int ksize, float modulation, int iterations, int route, float *d_out,
+		long out_stride);
+/* Kernel times of the context's last fmedian call (HIP events between the
+ * launches, one launch per iteration; waits for the call).  what[k] =
+ * 100*route + ksize of the kernel that ran.  Arrays of
+ * SGPU_FMEDIAN_MAX_LAUNCHES. */
+int sgpu_fmedian_last_kernel_ms(sgpu_context *ctx, float *ms, int *what, int *nlaunches);
+
 /* ---- star detection and star-based global registration ------------------- */
 
 /* Arithmetic: the specification in DESIGN.md 6f, restated in

@@ -55,6 +55,7 @@ EXPORTS = (
     "sgpu_bkg_rbf_check", "sgpu_subsky_rbf_planes_device", "sgpu_bkg_rbf_solve_device", "sgpu_bkg_rbf_last_kernel_ms",
     "sgpu_wavelet_check", "sgpu_wavelet_planes_device", "sgpu_wavelet_reconstruct_device",
     "sgpu_wrecons_planes_device", "sgpu_wavelet_last_kernel_ms",
+    "sgpu_fmedian_check", "sgpu_fmedian_planes_device", "sgpu_fmedian_last_kernel_ms",
     "sgpu_star_default_params", "sgpu_match_default_params", "sgpu_star_smooth_table", "sgpu_find_stars_device",
     "sgpu_star_last_candidates", "sgpu_star_last_kernel_ms", "sgpu_match_stars",
     "sgpu_psf_default_params", "sgpu_fit_stars_device", "sgpu_psf_last_kernel_ms",
@@ -420,6 +421,12 @@ def lib():
         L.sgpu_wrecons_planes_device.argtypes = [vp, vp, i, i, i, i, C.c_long, i, i, C.POINTER(f), vp, C.c_long]
         L.sgpu_wavelet_last_kernel_ms.restype = i
         L.sgpu_wavelet_last_kernel_ms.argtypes = [vp, C.POINTER(f), pi, pi]
+        L.sgpu_fmedian_check.restype = i
+        L.sgpu_fmedian_check.argtypes = [i, i, i, f, i]
+        L.sgpu_fmedian_planes_device.restype = i
+        L.sgpu_fmedian_planes_device.argtypes = [vp, vp, i, i, i, i, C.c_long, i, f, i, i, vp, C.c_long]
+        L.sgpu_fmedian_last_kernel_ms.restype = i
+        L.sgpu_fmedian_last_kernel_ms.argtypes = [vp, C.POINTER(f), pi, pi]
         L.sgpu_star_default_params.restype = None
         L.sgpu_star_default_params.argtypes = [C.POINTER(StarParams)]
         L.sgpu_match_default_params.restype = None

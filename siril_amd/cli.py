@@ -34,7 +34,12 @@ or with -rbf a thin-plate spline through the kept sample boxes, evaluated at eve
 (siril_amd/wavelets.py), type 1 linear or 2 B3 spline; writes the nbr_layers planes (the details, then the residual)
 as 32-bit <prefix><stem>_wavelet<k>.fit.  `python -m siril_amd.cli wrecons <image> c1 ... cn [-type=1|2] [-out=FILE]`
 sharpens with them: the planes of an n-layer transform weighted by c1 .. cn and summed, in one fused pass; writes one
-32-bit image, <stem>_wrecons.fit unless -out= names it."""
+32-bit image, <stem>_wrecons.fit unless -out= names it.
+
+`python -m siril_amd.cli fmedian <image> <ksize> <modulation> [-iter=N] [-out=FILE]`: the median filter
+(siril_amd/filters.py) of every layer of an image: ksize x ksize windows, ksize odd in 3 .. 15, the median blended
+with the sample by modulation in [0, 1], N = 1 .. 8 passes; writes one 32-bit image, <stem>_fmedian.fit unless -out=
+names it."""
 import sys
 import time
 
@@ -73,6 +78,12 @@ def main(argv=None):
         t0 = time.perf_counter()
         out = run_wrecons(argv)
         print(f"Reconstructed to {out} in {time.perf_counter() - t0:.3f} s")
+        return 0
+    if argv and argv[0] == "fmedian":
+        from siril_amd.filters import run_fmedian
+        t0 = time.perf_counter()
+        out = run_fmedian(argv)
+        print(f"Median filtered to {out} in {time.perf_counter() - t0:.3f} s")
         return 0
     if argv and argv[0] == "register":
         from siril_amd.registration import run_register
