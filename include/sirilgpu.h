@@ -230,9 +230,12 @@ long sgpu_last_exact_pixels(sgpu_context *ctx);
 
 /* Float WINSORIZED stacks of 65..128 frames (last launch of the last stack
  * call): the rejection rounds run as a head pass of SGPU_WZ_SPLIT rounds
- * (default 2) and two compacted tail passes over the pixels that need more.
+ * (default 2) and compacted tail passes over the pixels that need more: one
+ * pass that runs every remaining round when both sigmas are >= 3 (a second
+ * pass would take under half a percent of the pixels), two otherwise.
  * out[0] / out[1]: pixels that entered tail pass 1 / 2, summed over the
- * launch's chunks; 0 when the split did not run.  Read on request only (no
+ * launch's chunks; 0 when the split did not run, and out[1] is 0 on every
+ * launch with one tail pass.  Read on request only (no
  * work on the stack's own path).  Synchronises the context stream. */
 int sgpu_last_wz_deferred(sgpu_context *ctx, long long out[2]);
 

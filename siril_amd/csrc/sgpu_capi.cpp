@@ -552,12 +552,15 @@ int run_launch_body(sgpu_context *c, KParams k, bool has_shift) {
         k.fb2_count = (int *)c->fb2_count.p;
         HIP_TRY(hipMemsetAsync(k.fb2_count, 0, sizeof(int), s));
         // workspace: two buffers of rank records (R slots + moments, meta,
-        // round state, lists per pixel; stack_wz_launch.h), at most 2 GiB
+        // round state, lists per pixel; stack_wz_launch.h), at most 2 GiB --
+        // 2.5 GiB (kWzWsMax) where the fused form's deeper record can run --
         // and no more than this launch's pixels need
         const int npw = sorted_capacity(N);
         const long long R = npw <= 128 ? 64 : npw / 2 + 16;
         const size_t need = (size_t)(2 * k.npix * (R * 4 + 96) + (1 << 20));
-        const size_t ws = std::min(need, (size_t)2 << 30);
+        const bool deep = !k.frames16 && N >= sgpu::kWzDeepMinFrames && N <= 128 &&
+                          (wz_form == sgpu::kWzAuto || wz_form == sgpu::kWzFused);
+        const size_t ws = std::min(need, (size_t)(deep ? sgpu::kWzWsMax : sgpu::kWzWsTwoKernel));
         static const long long chunk = std::getenv("SGPU_WZ_CHUNK") ? std::atoll(std::getenv("SGPU_WZ_CHUNK")) : 0;
         k.wz_chunk = chunk;
         // per-chunk tails (fallback sorted + exact kernels of a chunk on a third

@@ -96,6 +96,17 @@ struct WzSplit {
     int *list_out, *cnt_out;
     int *def;                   // tail: the pass's word of KParams::wz_def, or null
 };
+// Workspace (sgpu_capi.cpp allocates it): the two-kernel forms use at most 2
+// GiB of it, the size their chunking was tuned at.  The fused form's record
+// (R = 48 slots, 280 bytes a pixel with moments, meta, state and lists) needs
+// 2.35 GB for the largest chunk the 23-bit stride allows (8 388 352 pixels):
+// at 2 GiB a 24 M-pixel launch would take four chunks where it took three.
+// Only a launch that can run the deeper record gets the larger cap: float, at
+// least kWzDeepMinFrames frames (real-slot bucket 96 up), fused or auto form.
+constexpr long long kWzWsTwoKernel = 2LL << 30;
+constexpr long long kWzWsMax = 5LL << 29;   // 2.5 GiB
+constexpr int kWzDeepMinFrames = 89;
+
 constexpr int kWzStripes = 1024;
 constexpr int kWzStripeStep = 16;   // ints between two stripe counters
 

@@ -12,9 +12,9 @@
 #include "stack_wz.h"
 
 #ifndef SGPU_WZ_TAIL_PASSES
-#define SGPU_WZ_TAIL_PASSES 2   // tail passes of the split rounds (1: one tail to the end; A/B)
+#define SGPU_WZ_TAIL_PASSES 0   // tail passes of the split rounds: 0 by the launch's sigmas (wz_tail_passes); 1 / 2 fixed (A/B)
 #endif
-static_assert(SGPU_WZ_TAIL_PASSES >= 1 && SGPU_WZ_TAIL_PASSES <= 2,
+static_assert(SGPU_WZ_TAIL_PASSES >= 0 && SGPU_WZ_TAIL_PASSES <= 2,
               "each of the two stripe-counter sets is zeroed once per chunk and appended to by one pass");
 
 #include <algorithm>

@@ -51,6 +51,28 @@
 #ifndef SGPU_WZ_KM
 #define SGPU_WZ_KM 8
 #endif
+// Ranks per end of the fused form (k_stack_wz_fused1 and the tail passes that
+// read what it leaves): its record lives in LDS, where 20 + 8 + 20 = 48 slots
+// are 12 KB per wave, 48 KB per block, three blocks in a CU's 160 KB -- the
+// occupancy the registers allow anyway -- so the deeper record costs no HBM
+// traffic, and about half of the pixels that went to the sorted kernel
+// because a walk left 16 ranks stay on the moment path (host counts on the
+// benchmark recipe, sigma 3/3: route 1 at depth 16 / 18 / 20 = 0.73 / 0.38 /
+// 0.34 % of the pixels; what is left are undecidable steps).  The two-kernel
+// forms keep SGPU_WZ_KT: their record is HBM traffic.  (16: the parent's
+// record, A/B.)
+// The buckets whose kernel fits four waves per SIMD in registers (real-slot
+// bound <= 88 at the parent of this change: at most 128 VGPRs) keep 16: four
+// blocks of 40 KB are exactly the CU's LDS, and 48 KB tiles would cost them
+// the fourth wave (no bench config runs there; not measured).  (With the LDS
+// sized by the launch the unshifted RSL = 88 kernel compiles to 131 VGPRs,
+// three waves: profiles/r13_wz_depth_kernel_resources.txt.)
+#ifndef SGPU_WZ_KT_FUSED
+#define SGPU_WZ_KT_FUSED 20
+#endif
+namespace sgpu {
+constexpr int wz_fused_kt(int rsl) { return rsl < kWzDeepMinFrames ? SGPU_WZ_KT : SGPU_WZ_KT_FUSED; }
+}
 // instrumentation hook of the host statistics tool (scripts/wzstat): empty in
 // every product build
 #ifndef SGPU_WZ_TRACE
@@ -115,12 +137,13 @@ SG_HD int wz_clip_counts(const TS &ts, int lo, int hi, float mf, float tl0, floa
 
 // Ranks kept per pixel: [0, KT), [mid0, mid0 + KM) around kept/2 and
 // [kept - KT, kept).  LDS layout [rank slot][pixel of the wave]: the wave's
-// pixels read consecutive words (no bank conflicts).
-template <int NP, int G>
+// pixels read consecutive words (no bank conflicts).  KTP: the depth per end
+// at NP <= 128 (R, the regions, the fetches and the compact copies follow it).
+template <int NP, int G, int KTP = SGPU_WZ_KT>
 struct RankStore {
     static constexpr int E = NP / G;
     static constexpr int PW = 64 / G;                      // pixels per wave
-    static constexpr int KT = NP <= 128 ? SGPU_WZ_KT : NP / 4;   // ranks per end
+    static constexpr int KT = NP <= 128 ? KTP : NP / 4;   // ranks per end
     static constexpr int KM = NP <= 128 ? SGPU_WZ_KM : 16; // ranks around the median
     static constexpr int R = 2 * KT + KM;                  // slots per pixel
     float *base;                                           // rank slot j of this pixel at base[j * stride + p]
@@ -218,8 +241,8 @@ struct RankStore {
     // a rank of the high region, [RSL - 7 - KT, RSL), and of the middle one,
     // [(RSL - 7) / 2 - KM / 2, RSL / 2 + KM / 2), are compile-time supersets
     // of every lane's ranges, so the stores stand in a straight line; a slot
-    // outside the lane's own range falls outside the region (offsets -7 .. 22
-    // and -4 .. 11 slots: no wrap back into it) and is dropped as in
+    // outside the lane's own range falls outside the region (offsets -7 ..
+    // KT + 6 and -4 .. 11 slots: no wrap back into it) and is dropped as in
     // store_buf.  Every rank of the three ranges is stored, so hi0 / mid0 /
     // mid1 are the unclipped ones -- what store() leaves for this wave.
     template <int RSL>
@@ -263,6 +286,21 @@ struct RankStore {
     // needs its test: ranks >= kept (the last 7 slots) and the last 4 middle
     // slots.  LDS stores of a lane complete in program order.  Leaves the
     // tile's R slots and hi0 / mid0 / mid1 as store_full leaves the record's.
+    // The depth KT moves none of this.  With kept in [RSL - 7, RSL]:
+    //   high    slots [RSL - 7 - KT, RSL), KT + 7 stores (27 at KT = 20, 23 at
+    //           16); slot e goes to tile row KT + KM + e - hi0, hi0 = kept - KT
+    //           in [RSL - 7 - KT, RSL - KT], so e - hi0 >= -7: at worst the
+    //           middle region's last 7 rows (KM >= 7), never the low region;
+    //   middle  slots [RSL / 2 - 4 - KM / 2, RSL / 2 + KM / 2), KM + 4 = 12
+    //           stores; row KT + e - mid0, mid0 = kept / 2 - KM / 2 >= RSL / 2
+    //           - 4 - KM / 2, so e - mid0 >= -4: the low region's last 4 rows
+    //           (KT >= KM / 2 >= 4);
+    //   low     slots [0, KT), stored last and whole, every lane's own ranks.
+    // 59 stores at KT = 20 (27 + 12 + 20), 51 at 16.  The high stores read the
+    // sorted column's top KT + 7 slots and the low ones its first KT: each
+    // sample is read where it already lives until the moments pass, which
+    // reads the whole column after them, so a deeper record lengthens no
+    // sample's life.
     template <int RSL>
     SG_HD void store_full_lds(const float (&v)[E]) {
         static_assert(G == 1 && RSL % 8 == 0 && RSL - 7 - KT >= KT && RSL <= E, "one lane per pixel, N >= 65");
@@ -688,10 +726,12 @@ SG_HD int wz_finish_cap(const RS &rs, int kept, double W1, double W2, float c0, 
 // moments about the first median c0 (one f64 pass; ranks >= kept hold +Inf
 // and add 0).  Returns 2 for the exact kernel (kept == 0), else 0.
 // GBUF: the record is the prep kernel's HBM one (RankStore::store_buf).
-template <int NP, int G, int RSL = NP / G, bool GBUF = false>
-SG_HD int wz_prepare(float (&v)[NP / G], int g, int kept, int kmin, int N, RankStore<NP, G> &rs, double &W1,
-                     double &W2, float &c0) {
+// RS: RankStore<NP, G> at any depth.
+template <int NP, int G, int RSL = NP / G, bool GBUF = false, class RS>
+SG_HD int wz_prepare(float (&v)[NP / G], int g, int kept, int kmin, int N, RS &rs, double &W1, double &W2,
+                     float &c0) {
     constexpr int E = NP / G;
+    static_assert(RS::E == E && RS::PW == 64 / G, "the record of this column layout");
     if (kept == 0) return 2;                // quickmedian of the whole stack (median_and_mean.c:1040)
     sort_col<NP, G, RSL>(v, g);
     if constexpr (G == 2) to_interleaved2<E>(v, g);
@@ -755,9 +795,9 @@ SG_HD int wz_prepare(float (&v)[NP / G], int g, int kept, int kmin, int N, RankS
 
 // One pixel after the gather, prep and rounds in one call on an LDS-style
 // rank store: the host simulation's entry (tests/hostsim); no kernel calls it.
-template <int NP, int G, int U16 = 0>
-SG_HD int wz_pixel(float (&v)[NP / G], int g, int kept, int kmin, int N, float slo_, float shi_,
-                   RankStore<NP, G> &rs, PixOut &o) {
+template <int NP, int G, int U16 = 0, class RS>
+SG_HD int wz_pixel(float (&v)[NP / G], int g, int kept, int kmin, int N, float slo_, float shi_, RS &rs,
+                   PixOut &o) {
     constexpr int E = NP / G;
     double W1, W2;
     float c0;
@@ -913,9 +953,10 @@ SG_HD int wave_min(int x) {
 // (wz_prepare1_sorted: everything after the sort -- the fused kernel sets its
 // tile's RankStore up between the two, so that nothing of it lives through
 // the sort)
-template <int RSL, bool LDS = false>
-SG_HD void wz_prepare1_sorted(const float (&v)[128], int kept, int N, RankStore<128, 1> &rs, double &W1, double &W2,
-                              float &c0) {
+// RS: RankStore<128, 1> at the depth of the form that runs
+template <int RSL, bool LDS = false, class RS>
+SG_HD void wz_prepare1_sorted(const float (&v)[128], int kept, int N, RS &rs, double &W1, double &W2, float &c0) {
+    static_assert(RS::E == 128 && RS::PW == 64, "one lane per pixel, N <= 128");
     constexpr int E = 128, K0 = RSL - 7;
     static_assert(RSL % 8 == 0 && RSL >= 72 && RSL <= E, "real-slot buckets of rs_pick(128, 1, N)");
     rs.kept = kept;
@@ -981,8 +1022,8 @@ SG_HD void wz_prepare1_sorted(const float (&v)[128], int kept, int N, RankStore<
     }
 }
 
-template <int RSL, bool LDS = false>
-SG_HD void wz_prepare1(float (&v)[128], int kept, int N, RankStore<128, 1> &rs, double &W1, double &W2, float &c0) {
+template <int RSL, bool LDS = false, class RS>
+SG_HD void wz_prepare1(float (&v)[128], int kept, int N, RS &rs, double &W1, double &W2, float &c0) {
     sort_col<128, 1, RSL>(v, 0);
     wz_prepare1_sorted<RSL, LDS>(v, kept, N, rs, W1, W2, c0);
 }
@@ -1196,14 +1237,33 @@ __global__ __launch_bounds__(64) void k_stack_wz_rounds_lds(KParams p, WzSplit s
 // path.  Only a deferring lane leaves something in the workspace, and leaves
 // all k_stack_wz_tail reads: its state, meta, moments, the compact copy of its
 // ranks in its tile of the (otherwise unwritten) record and the list entry.
-// Four waves x 10 KB of LDS per block; the register budget is the prep's
-// (three waves per SIMD), the rounds need fewer once the column is dead.
+// The record never leaves the CU, so from RSL = 96 up it is the deeper one
+// (wz_fused_kt: SGPU_WZ_KT_FUSED ranks per end, R = 48): four waves x 12 KB of
+// LDS per block, three blocks in a CU's 160 KB; the register budget is the
+// prep's (three waves per SIMD), the rounds need fewer once the column is
+// dead.
 template <int NP, int XF, int W, int RSL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, 8)))
 void k_stack_wz_fused1(KParams p, WzSplit sp) {
     static_assert(NP == 128, "one lane per pixel: N <= 128");
-    using RS = RankStore<NP, 1>;
-    __shared__ float s_rank[4 * RS::R * 64];
+    using RS = RankStore<NP, 1, wz_fused_kt(RSL)>;
+    static_assert(W * 4 * RS::R * 64 * sizeof(float) <= 160 * 1024, "W blocks' tiles in one CU's LDS");
+    // The tiles, 4 * R * 64 floats.  At depth SGPU_WZ_KT (RSL <= 88) declared
+    // with their size, 40 KB, as they always were: those kernels compile to
+    // the instructions they had.  At the deeper record they are sized by the
+    // launch (wz_fused_lds_bytes): declared with its size, 48 KB puts the
+    // compiler's occupancy estimate at three waves and its scheduler at ease
+    // with all 168 VGPRs of that budget -- the RSL = 104 kernel then peaks at
+    // the end of the gather and spills 4 dwords to scratch, where it took 158
+    // VGPRs and none with 40 KB; unsized, it compiles to 158 and no scratch.
+    float *s_rank;
+    if constexpr (wz_fused_kt(RSL) == SGPU_WZ_KT) {
+        __shared__ float s_sized[4 * RS::R * 64];
+        s_rank = s_sized;
+    } else {
+        extern __shared__ float s_unsized[];
+        s_rank = s_unsized;
+    }
     // the head block of this wave (wave-uniform; nothing below crosses waves)
     if (((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 >= p.wz_cnt) return;
     int kept = 0, bad = 0;
@@ -1300,9 +1360,10 @@ void k_stack_wz_fused1(KParams p, WzSplit sp) {
 // the head: result, fallback lists, or sp.list_out again.  Block b takes
 // stripe b % nstripes and every (gridDim / nstripes)-th tile of it; the
 // stripe's count is read on the device (no host read-back).
-template <int NP, int PG = NP / 64>
+// KTP: the depth of the records the head left (the fused kernel's is deeper).
+template <int NP, int PG = NP / 64, int KTP = SGPU_WZ_KT>
 __global__ __launch_bounds__(64) void k_stack_wz_tail(KParams p, WzSplit sp, int last) {
-    using RS = RankStore<NP, 1>;
+    using RS = RankStore<NP, 1, KTP>;
     __shared__ float s_rank[RS::R * 64];
     const int lane = (int)threadIdx.x;
     const int stripe = (int)(blockIdx.x % (unsigned)sp.nstripes);

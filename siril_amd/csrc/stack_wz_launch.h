@@ -144,8 +144,33 @@ KernelFn wz_prep_kernel(const KParams &p) {
 // rounds[b], so the chunk's fallback tails (third stream) see every append
 // and the next prep into the buffer finds records, state and lists free.
 // Tail pass 1 defers again, the last one finishes.  N > 128: global reads.
+// The tail passes read the head's records: the fused kernel's depth after it
+// (fused_kt: wz_fused_kt of the launch's real-slot bucket).
+//
+// Tail passes (wz_tail_passes): two where the second has work -- at sigma 2/2
+// four pixels in five outlast the head and a single pass to the end lost; one,
+// run to the end, when both sigmas are >= 3: pass 2 then takes 0.4 % of the
+// pixels in 0.06 ms of launch and latency per chunk on the stream everything
+// else waits for, and pass 1 finishing them costs less.
+// SGPU_WZ_TAIL_PASSES = 1 / 2 (compile time) fixes the count for A/B runs.
+inline int wz_tail_passes(const KParams &p) {
+    if (SGPU_WZ_TAIL_PASSES) return SGPU_WZ_TAIL_PASSES;
+    return p.sig0 >= 3.f && p.sig1 >= 3.f ? 1 : 2;
+}
+// LDS a fused block asks for at launch: the tiles of its four waves, R = 2 kt
+// + KM slots each, at the deeper record; at SGPU_WZ_KT the kernel declares
+// them itself (k_stack_wz_fused1)
+inline size_t wz_fused_lds_bytes(int kt) {
+    return kt == SGPU_WZ_KT ? 0 : (size_t)4 * (2 * kt + SGPU_WZ_KM) * 64 * sizeof(float);
+}
+template <int NP, int PG, int KTP>
+void wz_launch_tail(const KParams &q, const WzSplit &sp, int last, hipStream_t s) {
+    // 4 blocks per stripe: 4096 waves at 1024 stripes, the chip's 16 per CU
+    hipLaunchKernelGGL((k_stack_wz_tail<NP, PG, KTP>), dim3((unsigned)sp.nstripes * 4u), 64, 0, s, q, sp, last);
+}
 template <int NP, int PG, int U16>
-bool wz_launch_rounds(const KParams &p, const KParams &q, FusedFn fused_fn, int *const *lists, hipStream_t s) {
+bool wz_launch_rounds(const KParams &p, const KParams &q, FusedFn fused_fn, int fused_kt, int *const *lists,
+                      hipStream_t s) {
     if constexpr (NP > 128) {
         hipLaunchKernelGGL((k_stack_wz_rounds<NP, U16, PG>), (unsigned)((q.wz_cnt + 255) / 256), 256, 0, s, q);
     } else if constexpr (U16) {
@@ -167,19 +192,21 @@ bool wz_launch_rounds(const KParams &p, const KParams &q, FusedFn fused_fn, int 
             KParams qa = q;
             WzSplit spa = sp;
             void *args[] = {&qa, &spa};
-            if (hipLaunchKernel((const void *)fused_fn, dim3((nblk + 3) / 4), dim3(256), args, 0, s) != hipSuccess)
+            if (hipLaunchKernel((const void *)fused_fn, dim3((nblk + 3) / 4), dim3(256), args,
+                                wz_fused_lds_bytes(fused_kt), s) != hipSuccess)
                 return false;
         } else
             hipLaunchKernelGGL((k_stack_wz_rounds_lds<NP, 0, PG>), dim3(nblk), 64, 0, s, q, sp);
-        for (int pass = 0; sp.cap && pass < SGPU_WZ_TAIL_PASSES; pass++) {
+        const int passes = wz_tail_passes(p);
+        for (int pass = 0; sp.cap && pass < passes; pass++) {
             sp.list_in = lists[pass & 1];
             sp.cnt_in = p.wz_scnt + (pass & 1) * kWzStripes * kWzStripeStep;
             sp.list_out = lists[(pass + 1) & 1];
             sp.cnt_out = p.wz_scnt + ((pass + 1) & 1) * kWzStripes * kWzStripeStep;
             sp.def = p.wz_def ? p.wz_def + pass : nullptr;
-            // 4 blocks per stripe: 4096 waves at 1024 stripes, the chip's 16 per CU
-            hipLaunchKernelGGL((k_stack_wz_tail<NP, PG>), dim3((unsigned)sp.nstripes * 4u), 64, 0, s, q, sp,
-                               pass == SGPU_WZ_TAIL_PASSES - 1 ? 1 : 0);
+            const int last = pass == passes - 1 ? 1 : 0;
+            if (fused_fn && fused_kt != SGPU_WZ_KT) wz_launch_tail<NP, PG, SGPU_WZ_KT_FUSED>(q, sp, last, s);
+            else wz_launch_tail<NP, PG, SGPU_WZ_KT>(q, sp, last, s);
         }
     }
     return hipGetLastError() == hipSuccess;
@@ -217,12 +244,18 @@ int wz_launch(const KParams &p, hipStream_t s) {
     // the prep's lanes per pixel (the rounds kernels take it as a template argument)
     constexpr int PG = (NP == 128 && !U16) ? 1 : G;
     constexpr int PW = (NP == 128 && !U16) ? SGPU_WZ_PREP_W128_G1 : W;
-    constexpr int R = RankStore<NP, PG>::R;
     const bool fused = NP == 128 && !U16 &&
                        (p.wz_form == kWzFused || (p.wz_form == kWzAuto && wz_fused_auto(p)));
+    // slots of the record of the form that runs (chunk size, carving)
+    int fused_kt = SGPU_WZ_KT;
+    if constexpr (NP == 128 && !U16) fused_kt = wz_fused_kt(rs_pick_prep1(p.nframes));
+    const int R = fused ? 2 * fused_kt + RankStore<NP, PG>::KM : RankStore<NP, PG>::R;
     const bool ovl = !fused && p.wz_form != kWzSerial && NP <= 128;
     const int nbuf = ovl ? 2 : 1;
-    const long long ch = wz_chunk_pixels(NP, R, p.wz_ws_bytes, nbuf, p.npix, p.wz_chunk);
+    // the fused form's deeper record may use the whole workspace; the other
+    // forms chunk within kWzWsTwoKernel of it, as they were measured
+    const long long ws_bytes = fused ? p.wz_ws_bytes : std::min(p.wz_ws_bytes, kWzWsTwoKernel);
+    const long long ch = wz_chunk_pixels(NP, R, ws_bytes, nbuf, p.npix, p.wz_chunk);
     if (ch <= 0) return 1;
     WzAux *aux = nullptr;
     hipStream_t sp = s;                      // the prep kernels' stream
@@ -245,7 +278,7 @@ int wz_launch(const KParams &p, hipStream_t s) {
     }
     if (!fused && !(prep_fn = wz_prep_kernel<NP, PG, PW, U16>(p))) return -1;
     KParams q = p;
-    WzCarve cv{(char *)p.wz_ws, wz_buffer_bytes(p.wz_ws_bytes, nbuf), ch, R, {nullptr, nullptr}};
+    WzCarve cv{(char *)p.wz_ws, wz_buffer_bytes(ws_bytes, nbuf), ch, R, {nullptr, nullptr}};
     int k = 0;
     for (long long p0 = 0; p0 < p.npix; p0 += ch, k++) {
         const int b = k % nbuf;
@@ -264,7 +297,7 @@ int wz_launch(const KParams &p, hipStream_t s) {
         if (!fused && !launch_fn(prep_fn, (unsigned)((q.wz_cnt * PG + 255) / 256), 256, sp, q)) return -1;
         if (ovl && (hipEventRecord(aux->prep[b], sp) != hipSuccess || hipStreamWaitEvent(s, aux->prep[b], 0) != hipSuccess))
             return -1;
-        if (!wz_launch_rounds<NP, PG, U16>(p, q, fused_fn, cv.lists, s)) return -1;
+        if (!wz_launch_rounds<NP, PG, U16>(p, q, fused_fn, fused_kt, cv.lists, s)) return -1;
         if ((ovl || (fused && tails)) && hipEventRecord(aux->rounds[b], s) != hipSuccess) return -1;
         if constexpr (!U16) {
             if (tails) {
