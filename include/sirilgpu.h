@@ -840,6 +840,66 @@ int sgpu_fmedian_planes_device(sgpu_context *ctx, const void *d_in, int elem_siz
  * SGPU_FMEDIAN_MAX_LAUNCHES. */
 int sgpu_fmedian_last_kernel_ms(sgpu_context *ctx, float *ms, int *what, int *nlaunches);
 
+/* ---- stretches (mtf, autostretch, linstretch, asinh, ght, modasinh and the
+ * inverses of the last two) ---------------------------------------------- */
+
+/* The specification is DESIGN.md 6m (T0-T9), stated once in
+ * siril_amd/csrc/stretch_host.h and restated in tests/stretch_ref.py; parity
+ * with a Siril binary is unpinned.  A sample (elem_size 2: WORD, divided by
+ * 65535; 4: float) is widened to double and clipped to [0, 1]; everything up
+ * to the one rounding to float is double, rounded once per operation; log, exp
+ * and pow are built from + - * / and bit operations, so the host, the device
+ * and the restatement give the same bits.  A NaN stays a NaN. */
+enum { SGPU_STRETCH_MTF = 0, SGPU_STRETCH_LINEAR = 1, SGPU_STRETCH_ASINH = 2, SGPU_STRETCH_GHT = 3,
+	SGPU_STRETCH_INVGHT = 4, SGPU_STRETCH_MODASINH = 5, SGPU_STRETCH_INVMODASINH = 6 };
+/* colour model of a three-channel image (ght family; asinh takes HUMAN or EVEN, INDEPENDENT there means EVEN) */
+enum { SGPU_STRETCH_INDEPENDENT = 0, SGPU_STRETCH_HUMAN = 1, SGPU_STRETCH_EVEN = 2 };
+enum { SGPU_STRETCH_CLIP = 0, SGPU_STRETCH_RESCALE = 1, SGPU_STRETCH_RGBBLEND = 2 };
+#define SGPU_STRETCH_NCOEF 16
+typedef struct {
+	int function;           /* SGPU_STRETCH_* */
+	int model;              /* colour model; read only when nchannels == 3 */
+	int clipmode;           /* SGPU_STRETCH_CLIP .. RGBBLEND; read only with a luminance model */
+	int mask;               /* bit c set: channel c is stretched; the others pass through (nchannels == 3 only) */
+	double lo, m, hi;       /* mtf */
+	double D, B, LP, SP, HP; /* ght family: D is D_user, 0 .. 10, and exp(D_user) - 1 is what the formulas use */
+	double beta, offset;    /* asinh */
+	double BP;              /* linstretch */
+} sgpu_stretch_params;
+/* SGPU_OK, or SGPU_BAD_ARGUMENT with the reason in sgpu_last_error: an unknown
+ * function, model, clip mode or a mask outside 1 .. 7; mtf: hi <= lo, m
+ * outside (0, 1), lo or hi outside [0, 1]; linstretch: BP outside [0, 1);
+ * asinh: beta outside [1, 1000], offset outside [0, 1); ght family: D outside
+ * [0, 10], B outside [-5, 15], not 0 <= LP <= SP <= HP <= 1.  Host only. */
+int sgpu_stretch_check(const sgpu_stretch_params *p);
+/* The coefficient block the kernel is handed (T6), SGPU_STRETCH_NCOEF doubles;
+ * checks p first.  Host only; exposed so that it can be compared bit for bit. */
+int sgpu_stretch_coeffs(const sgpu_stretch_params *p, double *coeffs);
+/* T3: lo, m, hi of every plane (out[3*p + 0..2]) from the table that
+ * sgpu_norm_stats*_device fills (stats[4*p + 0..1] = median, mad; unit: 1 for
+ * float planes, 65535 for WORD planes) and its status.  nplanes = nimages *
+ * nchannels; linked != 0 gives the planes of one image the same three values.
+ * SGPU_BAD_ARGUMENT: a plane whose status is not 0, shadows_clip > 0 or not
+ * finite, target_bg outside (0, 1), a plane without spread (m would leave
+ * (0, 1)).  Host only. */
+int sgpu_autostretch_params(const double *stats, const int *status, int nimages, int nchannels, double unit,
+		int linked, double shadows_clip, double target_bg, double *out);
+/* Plane c of image i at d_in + (i*nchannels + c)*plane_stride samples, its
+ * result at d_out + (i*nchannels + c)*out_stride floats.  nparams is 1 (every
+ * plane), nimages (one block per image) or nimages*nchannels (one per plane;
+ * not with a luminance model, which needs an image's planes together).  One
+ * launch per parameter block, its coefficients in the kernel's arguments.
+ * With nchannels == 3 and a luminance model (or asinh) a pixel's three samples
+ * are read together.  Also SGPU_BAD_ARGUMENT: elem_size other than 2 or 4, a
+ * stride below width*height, an output that overlaps the input, a bad nparams.
+ * Asynchronous on the context's stream; copies nothing to the host. */
+int sgpu_stretch_planes_device(sgpu_context *ctx, const void *d_in, int elem_size, int nimages, int nchannels,
+		int width, int height, long plane_stride, const sgpu_stretch_params *params, int nparams,
+		float *d_out, long out_stride);
+/* Kernel time of the context's last stretch call (HIP events around its
+ * launches; waits for the call) and the number of launches. */
+int sgpu_stretch_last_kernel_ms(sgpu_context *ctx, float *ms, int *nlaunches);
+
 /* ---- star detection and star-based global registration ------------------- */
 
 /* Arithmetic: the specification in DESIGN.md 6f, restated in

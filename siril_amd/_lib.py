@@ -56,6 +56,8 @@ EXPORTS = (
     "sgpu_wavelet_check", "sgpu_wavelet_planes_device", "sgpu_wavelet_reconstruct_device",
     "sgpu_wrecons_planes_device", "sgpu_wavelet_last_kernel_ms",
     "sgpu_fmedian_check", "sgpu_fmedian_planes_device", "sgpu_fmedian_last_kernel_ms",
+    "sgpu_stretch_check", "sgpu_stretch_coeffs", "sgpu_autostretch_params", "sgpu_stretch_planes_device",
+    "sgpu_stretch_last_kernel_ms",
     "sgpu_star_default_params", "sgpu_match_default_params", "sgpu_star_smooth_table", "sgpu_find_stars_device",
     "sgpu_star_last_candidates", "sgpu_star_last_kernel_ms", "sgpu_match_stars",
     "sgpu_psf_default_params", "sgpu_fit_stars_device", "sgpu_psf_last_kernel_ms",
@@ -98,6 +100,12 @@ class StarParams(C.Structure):
     _fields_ = [(f, C.c_double) for f in ("ksigma", "smooth_sigma", "roundness_min", "min_amp", "cut", "min_fwhm",
                                           "sat")] + \
         [(f, C.c_int) for f in ("radius", "max_stars", "keep_candidates", "reserved")]
+
+
+class StretchParams(C.Structure):
+    """sgpu_stretch_params (include/sirilgpu.h)."""
+    _fields_ = [(f, C.c_int) for f in ("function", "model", "clipmode", "mask")] + \
+        [(f, C.c_double) for f in ("lo", "m", "hi", "D", "B", "LP", "SP", "HP", "beta", "offset", "BP")]
 
 
 class PsfParams(C.Structure):
@@ -427,6 +435,17 @@ def lib():
         L.sgpu_fmedian_planes_device.argtypes = [vp, vp, i, i, i, i, C.c_long, i, f, i, i, vp, C.c_long]
         L.sgpu_fmedian_last_kernel_ms.restype = i
         L.sgpu_fmedian_last_kernel_ms.argtypes = [vp, C.POINTER(f), pi, pi]
+        L.sgpu_stretch_check.restype = i
+        L.sgpu_stretch_check.argtypes = [C.POINTER(StretchParams)]
+        L.sgpu_stretch_coeffs.restype = i
+        L.sgpu_stretch_coeffs.argtypes = [C.POINTER(StretchParams), C.POINTER(C.c_double)]
+        L.sgpu_autostretch_params.restype = i
+        L.sgpu_autostretch_params.argtypes = [vp, vp, i, i, C.c_double, i, C.c_double, C.c_double, vp]
+        L.sgpu_stretch_planes_device.restype = i
+        L.sgpu_stretch_planes_device.argtypes = [vp, vp, i, i, i, i, i, C.c_long, C.POINTER(StretchParams), i, vp,
+                                                 C.c_long]
+        L.sgpu_stretch_last_kernel_ms.restype = i
+        L.sgpu_stretch_last_kernel_ms.argtypes = [vp, C.POINTER(f), pi]
         L.sgpu_star_default_params.restype = None
         L.sgpu_star_default_params.argtypes = [C.POINTER(StarParams)]
         L.sgpu_match_default_params.restype = None

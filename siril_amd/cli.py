@@ -39,7 +39,16 @@ sharpens with them: the planes of an n-layer transform weighted by c1 .. cn and 
 `python -m siril_amd.cli fmedian <image> <ksize> <modulation> [-iter=N] [-out=FILE]`: the median filter
 (siril_amd/filters.py) of every layer of an image: ksize x ksize windows, ksize odd in 3 .. 15, the median blended
 with the sample by modulation in [0, 1], N = 1 .. 8 passes; writes one 32-bit image, <stem>_fmedian.fit unless -out=
-names it."""
+names it.
+
+The stretches (siril_amd/stretch.py), each on every layer of an image, each writing one 32-bit image,
+<stem>_<command>.fit unless -out= names it:
+`python -m siril_amd.cli mtf <image> <low> <mid> <high> [channels] [-out=FILE]`,
+`autostretch <image> [-linked] [shadowsclip [targetbg]] [-out=FILE]` (defaults -2.8 and 0.25),
+`linstretch <image> -BP= [-out=FILE]`, `asinh <image> [-human] <stretch> [offset] [-out=FILE]`,
+`ght <image> -D= [-B=] [-LP=] [-SP=] [-HP=] [-human|-even|-independent] [-clipmode=clip|rescale|rgbblend] [channels]
+[-out=FILE]`, and `invght`, `modasinh`, `invmodasinh` with ght's options (the modasinh pair has no -B=); channels is
+one of R, G, B, RG, RB, GB."""
 import sys
 import time
 
@@ -84,6 +93,12 @@ def main(argv=None):
         t0 = time.perf_counter()
         out = run_fmedian(argv)
         print(f"Median filtered to {out} in {time.perf_counter() - t0:.3f} s")
+        return 0
+    if argv and argv[0] in ("mtf", "autostretch", "linstretch", "asinh", "ght", "invght", "modasinh", "invmodasinh"):
+        from siril_amd.stretch import run_stretch
+        t0 = time.perf_counter()
+        out = run_stretch(argv)
+        print(f"Stretched ({argv[0]}) to {out} in {time.perf_counter() - t0:.3f} s")
         return 0
     if argv and argv[0] == "register":
         from siril_amd.registration import run_register

@@ -241,6 +241,8 @@ void sgpu_release(sgpu_context *c) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->med_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->str_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->own) (void)hipStreamDestroy(c->own);
     delete c;
 }

@@ -173,6 +173,9 @@ struct sgpu_context {
     hipEvent_t med_ev[SGPU_FMEDIAN_MAX_LAUNCHES + 1] = {}; // one before every launch of a call, one after the last
     int med_what[SGPU_FMEDIAN_MAX_LAUNCHES] = {};          // 100*route + ksize, per launch
     int med_launches = 0;
+    // stretches: one event before the first launch of a call, one after the last
+    hipEvent_t str_ev[2] = {};
+    int str_launches = 0;
 
     void release_all() {
         for (sgpu_host::DevBuf *b : {&fb_list, &fb_count, &counts, &scratch, &scale, &offset, &mul,
