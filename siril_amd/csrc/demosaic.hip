@@ -20,7 +20,6 @@
 // exactly the unnormalised one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <cstdlib>
 
 namespace sgpu {
 namespace dm {
@@ -34,7 +33,6 @@ struct Img {
     int W, H;
     unsigned char cf[4];            // cfarray[row & 1][col & 1]: 0 R, 1 G, 2 B
     const unsigned *mm;             // ordered-uint min / max of the input
-    int remap;                      // 1: XCD-contiguous tile order (DM_XY)
 };
 
 __device__ __forceinline__ unsigned f2ord(float v) {
@@ -62,21 +60,22 @@ __device__ __forceinline__ void norm_consts(const Img &g, float &mn, float &fact
     factor = 65535.0f / (mx - mn);
 }
 
-// 64 x 4 pixel tiles.  remap: the dispatcher deals consecutive workgroups
-// round-robin over the 8 XCDs (each with its own L2), so the tiles above and
-// below a tile -- whose rows its stencils read -- ran on other XCDs and every
-// tile fetched its halo rows from HBM (RCD moved ~64 planes of traffic for
-// ~24 plane touches).  The tiles are renumbered so that each XCD walks one
-// contiguous band of tile rows.
-__device__ __forceinline__ void dm_tile(const Img &g, int &bx, int &by) {
+// 64 x 4 pixel tiles.  The dispatcher deals consecutive workgroups
+// round-robin over the 8 XCDs (each with its own L2), so in its order the
+// tiles above and below a tile -- whose rows its stencils read -- ran on other
+// XCDs and every tile fetched its halo rows from HBM (RCD moved ~64 planes of
+// traffic for ~24 plane touches).  The tiles are renumbered so that each XCD
+// walks one contiguous band of tile rows (a grid that is no multiple of 8
+// keeps the dispatcher's order).
+__device__ __forceinline__ void dm_tile(int &bx, int &by) {
     const unsigned total = gridDim.x * gridDim.y, L = blockIdx.y * gridDim.x + blockIdx.x;
-    const unsigned w = (g.remap && total % 8u == 0u) ? (L % 8u) * (total / 8u) + L / 8u : L;
+    const unsigned w = (total % 8u == 0u) ? (L % 8u) * (total / 8u) + L / 8u : L;
     bx = (int)(w % gridDim.x);
     by = (int)(w / gridDim.x);
 }
 #define DM_XY                                                        \
     int bx_, by_;                                                    \
-    dm_tile(g, bx_, by_);                                            \
+    dm_tile(bx_, by_);                                               \
     const int x = bx_ * 64 + (threadIdx.x & 63);                     \
     const int y = by_ * 4 + (threadIdx.x >> 6);                      \
     if (x >= g.W || y >= g.H) return;                                \
@@ -165,57 +164,17 @@ __device__ __forceinline__ float hpf2(float m3, float m2, float m1, float c, flo
     return t * t;
 }
 
-// step 1.1: squared vertical / horizontal high-pass
-__global__ __launch_bounds__(256) void k_hv(Img g, const float *cfa, float *V, float *Hh) {
-    DM_XY
-    float v = 0.f, h = 0.f;
-    if (y >= 3 && y < g.H - 3 && x >= 4 && x < g.W - 4)
-        v = hpf2(cfa[p - 3 * W], cfa[p - 2 * W], cfa[p - W], cfa[p], cfa[p + W], cfa[p + 2 * W], cfa[p + 3 * W]);
-    if (y >= 4 && y < g.H - 4 && x >= 3 && x < g.W - 3)
-        h = hpf2(cfa[p - 3], cfa[p - 2], cfa[p - 1], cfa[p], cfa[p + 1], cfa[p + 2], cfa[p + 3]);
-    V[p] = v;
-    Hh[p] = h;
-}
-
-// step 1.2 VH_Dir; step 2 low pass; step 4.0 diagonal high-pass
-__global__ __launch_bounds__(256) void k_dir(Img g, const float *cfa, const float *V, const float *Hh, float *VH,
-                                             float *LP, float *P, float *Q) {
-    DM_XY
-    float vh = 0.f;
-    if (inr(g, y, x, 4)) {
-        const float vs = fmaxf(EPSSQ, (V[p - W] + V[p]) + V[p + W]);
-        const float hs = fmaxf(EPSSQ, (Hh[p - 1] + Hh[p]) + Hh[p + 1]);
-        vh = vs / (vs + hs);
-    }
-    VH[p] = vh;
-    const bool ng = fc(g, y, x) != 1;
-    float lp = 0.f, pp = 0.f, qq = 0.f;
-    if (ng && inr(g, y, x, 2)) {
-        lp = cfa[p] + 0.5f * (((cfa[p - W] + cfa[p + W]) + cfa[p - 1]) + cfa[p + 1]);
-        lp = lp + 0.25f * (((cfa[p - W - 1] + cfa[p - W + 1]) + cfa[p + W - 1]) + cfa[p + W + 1]);
-    }
-    if (ng && inr(g, y, x, 3)) {
-        pp = hpf2(cfa[p - 3 * W - 3], cfa[p - 2 * W - 2], cfa[p - W - 1], cfa[p], cfa[p + W + 1], cfa[p + 2 * W + 2],
-                  cfa[p + 3 * W + 3]);
-        qq = hpf2(cfa[p - 3 * W + 3], cfa[p - 2 * W + 2], cfa[p - W + 1], cfa[p], cfa[p + W - 1], cfa[p + 2 * W - 2],
-                  cfa[p + 3 * W - 3]);
-    }
-    LP[p] = lp;
-    P[p] = pp;
-    Q[p] = qq;
-}
-
-// k_hv, k_dir and k_pq in one pass (round 6): VH_Dir from the six high-pass
-// values it reads, recomputed from the CFA plane instead of stored in V / Hh
-// and re-read, and the PQ ratio of step 4.1 from the six diagonal high-pass
-// values instead of the P / Q planes -- 4 planes written (VH, LP, PQ) and 1 read
-// (cfa) instead of 2 + 4 + 1 written and 1 + 3 + 2 read by the three kernels.
-// Inside inr(4) every V / H / P / Q value the ratios read is in its own
-// non-zero range (V: rows [3, H-3), H: columns [3, W-3), P / Q: red / blue
-// sites in inr(3), and a red / blue site's diagonals are red / blue), so the
-// recomputed values are the stored ones; where k_pq writes nothing the plane
-// keeps the low-pass value, as k_pq's in-place buffer did.  Same
-// expressions, same order: bitwise the three-kernel planes.
+// steps 1.1-1.2 (VH_Dir), 2 (low pass) and 4.0-4.1 (PQ_Dir) in one pass
+// (round 6): VH_Dir from the six squared vertical / horizontal high-pass
+// values it reads and the PQ ratio from the six diagonal ones, each
+// recomputed from the CFA plane -- 3 planes written (VH, LP, PQ) and 1 read
+// (cfa).  The step-per-kernel form it replaced (V / H, then VH + LP + P / Q,
+// then PQ in place over LP) wrote 7 planes and read 6: 1.10 ms per 6000x4000
+// frame against 0.90 ms.  Inside inr(4) every high-pass value the ratios read
+// lies where the reference computes it (V: rows [3, H-3), H: columns
+// [3, W-3), P / Q: red / blue sites in inr(3), and a red / blue site's
+// diagonals are red / blue); where step 4.1 writes nothing the PQ plane
+// holds the low-pass value, as the reference's in-place buffer does.
 __global__ __launch_bounds__(256) void k_dir_pq(Img g, const float *cfa, float *VH, float *LP, float *PQ) {
     DM_XY
     auto vpf = [&](long long q) {
@@ -289,20 +248,6 @@ __global__ __launch_bounds__(256) void k_green(Img g, const float *cfa, const fl
     const float nb = 0.25f * ((VH[p - W - 1] + VH[p - W + 1]) + (VH[p + W - 1] + VH[p + W + 1]));
     const float d = disc(VH[p], nb);
     G[p] = d * (H_Est - V_Est) + V_Est;
-}
-
-// step 4.1: PQ_Dir over the low-pass buffer (in place: reads only P / Q)
-__global__ __launch_bounds__(256) void k_pq(Img g, const float *P, const float *Q, float *LPQ) {
-    DM_XY
-    if (fc(g, y, x) == 1 || !inr(g, y, x, 4)) return;
-    const float ps = fmaxf(EPSSQ, (P[p - W - 1] + P[p]) + P[p + W + 1]);
-    const float qs = fmaxf(EPSSQ, (Q[p - W + 1] + Q[p]) + Q[p + W - 1]);
-    LPQ[p] = ps / (ps + qs);
-}
-
-// native value of colour c at (r, x), else 0 (rgb[c] before step 4.2)
-__device__ __forceinline__ float nat(const Img &g, const float *cfa, long long q, int r, int x, int c) {
-    return fc(g, r, x) == c ? cfa[q] : 0.f;
 }
 
 // step 4.2: red at blue sites, blue at red sites; native values elsewhere
@@ -413,226 +358,47 @@ __global__ __launch_bounds__(256) void k_final(Img g, const T *buf, const float 
 // ---------------------------------------------------------------- bayerfast
 // BAYER_BILINEAR: librtprocess bayerfast_demosaic (demosaicing_rtp.cpp:147-151,
 // 318-323; RawTherapee fast_demosaic), restated in oracle/demosaic_ref.py
-// (parity with librtprocess unpinned).  Two stencil passes in the
-// reference's expression order, f32 without contraction:
-//   k_bf_green: the green plane (raw at green sites, the gradient-weighted
-//     mean of the four neighbours at red / blue sites, rows / columns
-//     [3, -3): what the interior reads) -- the four reciprocals and the
-//     division per red / blue site are done once;
-//   k_bf_final: red / blue from the green plane (diagonal colour difference
-//     at red / blue sites, cardinal at green sites, the diagonal one of the
-//     neighbours recomputed from four green reads), the 5-pixel border
-//     (border_interpolate), the wrapper's inverse map.
-// (One pass recomputing every green it needs, 13 per pixel, was VALU-bound
-// on the divisions: 2.03 ms per 6000 x 4000 frame, profiles/r05d_b_bayerfast.)
+// (parity with librtprocess unpinned), in the reference's expression order,
+// f32 without contraction.  Its two steps:
+//   green: raw at green sites, the gradient-weighted mean of the four
+//     neighbours at red / blue sites (rows / columns [3, -3): what the
+//     interior reads) -- four reciprocals and a division per red / blue site;
+//   red / blue from the green plane: the diagonal colour difference at red /
+//     blue sites, the cardinal one at green sites (over its four neighbours'
+//     own or diagonal estimates); the 5-pixel border (border_interpolate);
+//     the wrapper's inverse map.
+//
+// One tiled pass, k_bf_pairs: a workgroup owns a 64 x 32 tile of the output.
+// It loads the normalised raw values of the tile and a 4-pixel halo into LDS
+// (coalesced rows, each value converted once with the wrapper's (v - mn) *
+// factor), computes the green plane of the tile and a 2-pixel halo into LDS,
+// then the three colours, reading green and raw from LDS: the green plane
+// never reaches HBM.  The border (!inr(5)) keeps the global
+// border_interpolate restatement.
+//
+// Site pairs: the green sites of a Bayer CFA form a checkerboard, so every
+// horizontal pair of columns (2i, 2i + 1) holds one green and one red / blue
+// site.  A lane owns one pair in every stage, so no branch diverges on the
+// site colour, and the diagonal estimate of the red / blue site's missing
+// colour is computed once into a third LDS plane D (one word per red / blue
+// site, tile + 1-pixel halo) that the green sites read.
+//
+// The forms this one beat, all bitwise equal to it (profiles/README.md, rows
+// r05d, r06h, r06s): one pass recomputing every green it needs, 13 per
+// pixel, was VALU-bound on the divisions (2.03 ms per 6000 x 4000 frame);
+// two passes with the green plane in HBM wrote and re-read it, and each
+// thread fetched its ~20 neighbours through L1 (0.621 ms); the same LDS
+// tiles with one pixel per lane ran the green-site and the red / blue branch
+// one after the other in every wave and evaluated each diagonal estimate
+// five times (0.365 ms against 0.256 ms).
 constexpr int BF_BORDER = 5;
 constexpr float BF_CLIP = 4.f * 65535.f;   // clip_pt = 4 * 65535 * initGain, initGain = 1.0
 
-template <class T>
-struct BfSrc {
-    const T *buf;
-    int W;
-    float mn, factor;
-    __device__ __forceinline__ float raw(int y, int x) const { return (ld(buf, (long long)y * W + x) - mn) * factor; }
-};
 __device__ __forceinline__ float bf_min(float v) { return v < BF_CLIP ? v : BF_CLIP; }   // std::min(clip_pt, v)
 
-template <class T>
-__global__ __launch_bounds__(256) void k_bf_green(Img g, const T *buf, float *G) {
-    DM_XY
-    (void)W;
-    float mn, factor;
-    norm_consts(g, mn, factor);
-    const BfSrc<T> b{buf, g.W, mn, factor};
-    const float c = b.raw(y, x);
-    if (fc(g, y, x) == 1 || !inr(g, y, x, BF_BORDER - 2)) {
-        G[p] = c;                                  // outside [3, -3) nothing reads it as an estimate
-        return;
-    }
-    const float n1 = b.raw(y - 1, x), s1 = b.raw(y + 1, x), w1 = b.raw(y, x - 1), e1 = b.raw(y, x + 1);
-    float t;
-    t = (1.f + fabsf(c - b.raw(y - 2, x))) + fabsf(n1 - s1);
-    const float wtu = 1.f / (t * t);
-    t = (1.f + fabsf(c - b.raw(y + 2, x))) + fabsf(s1 - n1);
-    const float wtd = 1.f / (t * t);
-    t = (1.f + fabsf(c - b.raw(y, x - 2))) + fabsf(w1 - e1);
-    const float wtl = 1.f / (t * t);
-    t = (1.f + fabsf(c - b.raw(y, x + 2))) + fabsf(e1 - w1);
-    const float wtr = 1.f / (t * t);
-    G[p] = (((wtu * n1 + wtd * s1) + wtl * w1) + wtr * e1) / (((wtu + wtd) + wtl) + wtr);
-}
-
-// colour k (0 red, 2 blue) at the red / blue site q = (y, x): native, or the
-// colour difference of the four diagonals
-template <class T>
-__device__ __forceinline__ float bf_rb_site(const Img &g, const BfSrc<T> &b, const float *G, int y, int x, int k) {
-    if (fc(g, y, x) == k) return b.raw(y, x);
-    const long long W = g.W, q = (long long)y * W + x;
-    const float gd = ((G[q - W - 1] + G[q - W + 1]) + G[q + W + 1]) + G[q + W - 1];
-    const float rd = ((b.raw(y - 1, x - 1) + b.raw(y - 1, x + 1)) + b.raw(y + 1, x + 1)) + b.raw(y + 1, x - 1);
-    return G[q] - 0.25f * (gd - bf_min(rd));
-}
-
-template <class T, class O>
-__global__ __launch_bounds__(256) void k_bf_final(Img g, const T *buf, const float *G, O *rgb, int byte) {
-    DM_XY
-    float mn, factor;
-    norm_consts(g, mn, factor);
-    const float invfactor = (float)(1.0 / (double)factor);
-    const BfSrc<T> b{buf, g.W, mn, factor};
-    float o[3];
-    if (!inr(g, y, x, BF_BORDER)) {
-        border(g, buf, mn, factor, y, x, o);      // border_interpolate(bord = 5) on the normalised data
-    } else {
-        const float g0 = G[p];
-        float r, bl;
-        if (fc(g, y, x) != 1) {
-            r = bf_rb_site(g, b, G, y, x, 0);
-            bl = bf_rb_site(g, b, G, y, x, 2);
-        } else {
-            const float gN = G[p - W], gW = G[p - 1], gE = G[p + 1], gS = G[p + W];
-            const float gsum = ((gN + gW) + gE) + gS;
-            float v[2];
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const int k = 2 * q;
-                const float xs = ((bf_rb_site(g, b, G, y - 1, x, k) + bf_rb_site(g, b, G, y, x - 1, k)) +
-                                  bf_rb_site(g, b, G, y, x + 1, k)) +
-                                 bf_rb_site(g, b, G, y + 1, x, k);
-                v[q] = g0 - 0.25f * (gsum - bf_min(xs));
-            }
-            r = v[0];
-            bl = v[1];
-        }
-        o[0] = fmaxf(0.f, r);
-        o[1] = fmaxf(0.f, g0);
-        o[2] = fmaxf(0.f, bl);
-    }
-    const long long n = (long long)g.W * g.H;
-#pragma unroll
-    for (int k = 0; k < 3; k++) st(rgb, k * n + p, o[k] * invfactor + mn, byte);
-}
-
-// One tiled pass (round 6): a workgroup owns a 64 x 32 tile of the output.
-// It loads the normalised raw values of the tile and a 4-pixel halo into LDS
-// (coalesced rows, each value converted once with the wrapper's (v - mn) *
-// factor), computes the green plane of the tile and a 2-pixel halo into LDS
-// with k_bf_green's expressions, then the three colours with k_bf_final's,
-// reading G and raw from LDS: the green plane never reaches HBM (the
-// two-pass form wrote and re-read it, and each thread fetched its ~20
-// neighbours through L1).  Same expressions in the same order, so the
-// result is bitwise the two-pass one.  The border (!inr(5)) keeps the global
-// border_interpolate restatement.
 constexpr int BFT_W = 64, BFT_H = 32;
 constexpr int BFR_W = BFT_W + 8, BFR_H = BFT_H + 8;   // raw: halo 4
 constexpr int BFG_W = BFT_W + 4, BFG_H = BFT_H + 4;   // green: halo 2
-
-template <class T, class O>
-__global__ __launch_bounds__(256) void k_bf_tiled(Img g, const T *buf, O *rgb, int byte) {
-    __shared__ float s_raw[BFR_H * BFR_W];
-    __shared__ float s_g[BFG_H * BFG_W];
-    int bx, by;
-    dm_tile(g, bx, by);
-    const int x0 = bx * BFT_W, y0 = by * BFT_H;
-    const int W = g.W, H = g.H;
-    float mn, factor;
-    norm_consts(g, mn, factor);
-    // raw tile rows [y0 - 4, y0 + 20), columns [x0 - 4, x0 + 68); outside the
-    // image: 0 (never read by an in-image estimate, see below)
-    for (int i = threadIdx.x; i < BFR_H * BFR_W; i += 256) {
-        const int ry = i / BFR_W, rx = i % BFR_W;
-        const int yy = y0 - 4 + ry, xx = x0 - 4 + rx;
-        s_raw[i] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? (ld(buf, (long long)yy * W + xx) - mn) * factor : 0.f;
-    }
-    __syncthreads();
-    auto R = [&](int yy, int xx) { return s_raw[(yy - y0 + 4) * BFR_W + (xx - x0 + 4)]; };
-    // green of the tile and a 2-pixel halo (k_bf_green): G at (yy, xx) reads
-    // raw within 2 of it, inside the raw halo of 4
-    for (int i = threadIdx.x; i < BFG_H * BFG_W; i += 256) {
-        const int gy = i / BFG_W, gx = i % BFG_W;
-        const int yy = y0 - 2 + gy, xx = x0 - 2 + gx;
-        float v = 0.f;
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
-            const float c = R(yy, xx);
-            if (fc(g, yy, xx) == 1 || !inr(g, yy, xx, BF_BORDER - 2)) {
-                v = c;
-            } else {
-                const float n1 = R(yy - 1, xx), s1 = R(yy + 1, xx), w1 = R(yy, xx - 1), e1 = R(yy, xx + 1);
-                float t;
-                t = (1.f + fabsf(c - R(yy - 2, xx))) + fabsf(n1 - s1);
-                const float wtu = 1.f / (t * t);
-                t = (1.f + fabsf(c - R(yy + 2, xx))) + fabsf(s1 - n1);
-                const float wtd = 1.f / (t * t);
-                t = (1.f + fabsf(c - R(yy, xx - 2))) + fabsf(w1 - e1);
-                const float wtl = 1.f / (t * t);
-                t = (1.f + fabsf(c - R(yy, xx + 2))) + fabsf(e1 - w1);
-                const float wtr = 1.f / (t * t);
-                v = (((wtu * n1 + wtd * s1) + wtl * w1) + wtr * e1) / (((wtu + wtd) + wtl) + wtr);
-            }
-        }
-        s_g[i] = v;
-    }
-    __syncthreads();
-    auto Gg = [&](int yy, int xx) { return s_g[(yy - y0 + 2) * BFG_W + (xx - x0 + 2)]; };
-    // bf_rb_site on the LDS planes
-    auto rb_site = [&](int yy, int xx, int k) {
-        if (fc(g, yy, xx) == k) return R(yy, xx);
-        const float gd = ((Gg(yy - 1, xx - 1) + Gg(yy - 1, xx + 1)) + Gg(yy + 1, xx + 1)) + Gg(yy + 1, xx - 1);
-        const float rd = ((R(yy - 1, xx - 1) + R(yy - 1, xx + 1)) + R(yy + 1, xx + 1)) + R(yy + 1, xx - 1);
-        return Gg(yy, xx) - 0.25f * (gd - bf_min(rd));
-    };
-    const float invfactor = (float)(1.0 / (double)factor);
-    const long long n = (long long)W * H;
-    const int x = x0 + (int)(threadIdx.x & 63);
-#pragma unroll
-    for (int j = 0; j < BFT_H / 4; j++) {
-        const int y = y0 + (int)(threadIdx.x >> 6) + 4 * j;
-        if (x >= W || y >= H) continue;
-        float o[3];
-        if (!inr(g, y, x, BF_BORDER)) {
-            border(g, buf, mn, factor, y, x, o);
-        } else {
-            const float g0 = Gg(y, x);
-            float r, bl;
-            if (fc(g, y, x) != 1) {
-                r = rb_site(y, x, 0);
-                bl = rb_site(y, x, 2);
-            } else {
-                const float gsum = ((Gg(y - 1, x) + Gg(y, x - 1)) + Gg(y, x + 1)) + Gg(y + 1, x);
-                float v[2];
-#pragma unroll
-                for (int q = 0; q < 2; q++) {
-                    const int k = 2 * q;
-                    const float xs = ((rb_site(y - 1, x, k) + rb_site(y, x - 1, k)) + rb_site(y, x + 1, k)) +
-                                     rb_site(y + 1, x, k);
-                    v[q] = g0 - 0.25f * (gsum - bf_min(xs));
-                }
-                r = v[0];
-                bl = v[1];
-            }
-            o[0] = fmaxf(0.f, r);
-            o[1] = fmaxf(0.f, g0);
-            o[2] = fmaxf(0.f, bl);
-        }
-        const long long p = (long long)y * W + x;
-#pragma unroll
-        for (int k = 0; k < 3; k++) st(rgb, k * n + p, o[k] * invfactor + mn, byte);
-    }
-}
-
-// Site pairs (round 6, the default for Bayer patterns): the green sites of a
-// Bayer CFA form a checkerboard, so every horizontal pair of columns (2i,
-// 2i + 1) holds one green and one red / blue site.  k_bf_tiled gives one
-// lane one pixel, so each wave ran the green-site branch and the red / blue
-// branch one after the other (half its lanes masked in each), and a green
-// site's red and blue recomputed the diagonal colour difference of each of
-// its four neighbours (every such estimate was evaluated five times).  Here
-// a lane owns one pair in every stage, so no branch diverges on the site
-// colour, and the diagonal estimate of the red / blue site's missing colour
-// is computed once into a third LDS plane D (one word per red / blue site,
-// tile + 1-pixel halo) that the green sites read.  Same expressions in the
-// same order (D holds the float rb_site returned), so the output is bitwise
-// k_bf_tiled's.
 constexpr int BFD_W = BFT_W / 2 + 1, BFD_H = BFT_H + 2;   // D: red / blue sites of the tile + halo 1
 
 // Pair reads: a lane's pair (xx, xx + 1), xx even, sits at an even offset of
@@ -660,7 +426,7 @@ __global__ __launch_bounds__(256) void k_bf_pairs(Img g, const T *buf, O *rgb, i
     __shared__ __align__(16) float s_g[BFG_H * BFG_W];
     __shared__ __align__(16) float s_d[BFD_H * BFD_W];
     int bx, by;
-    dm_tile(g, bx, by);
+    dm_tile(bx, by);
     const int x0 = bx * BFT_W, y0 = by * BFT_H;   // x0 even
     const int W = g.W, H = g.H;
     float mn, factor;
@@ -802,626 +568,39 @@ __global__ __launch_bounds__(256) void k_bf_pairs(Img g, const T *buf, O *rgb, i
     }
 }
 
-// Bayer: green on a checkerboard (the pair kernel's premise)
-inline bool bayer_checkerboard(const Img &g) {
-    return (g.cf[0] == 1) == (g.cf[3] == 1) && (g.cf[1] == 1) == (g.cf[2] == 1) && (g.cf[0] == 1) != (g.cf[1] == 1);
-}
-
-// ws: g.W * g.H floats (the green plane; the two-pass form only).
-// SGPU_BF_TWOPASS=1 selects the two-pass form, SGPU_BF_TILED=1 the
-// one-pixel-per-lane tiled pass (A/B).
+// The pair kernel's premise, green on a checkerboard, holds for every pattern
+// the entry points admit (sgpu_demosaic.cpp asserts it on its pattern table).
 template <class T, class O>
-int launch_bayerfast(Img g, const T *buf, O *rgb, int byte, float *ws, hipStream_t s) {
-    static const bool two = std::getenv("SGPU_BF_TWOPASS") && std::atoi(std::getenv("SGPU_BF_TWOPASS")) != 0;
-    static const bool tiled = std::getenv("SGPU_BF_TILED") && std::atoi(std::getenv("SGPU_BF_TILED")) != 0;
-    if (!two && !tiled && bayer_checkerboard(g)) {
-        const dim3 grid((g.W + BFT_W - 1) / BFT_W, (g.H + BFT_H - 1) / BFT_H);
-        // pair stores: even width and an output aligned to the pair size
-        const int vec = (g.W % 2 == 0) && (reinterpret_cast<uintptr_t>(rgb) % (2 * sizeof(O)) == 0);
-        hipLaunchKernelGGL((k_bf_pairs<T, O>), grid, dim3(256), 0, s, g, buf, rgb, byte, vec);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    if (!two) {
-        const dim3 grid((g.W + BFT_W - 1) / BFT_W, (g.H + BFT_H - 1) / BFT_H);
-        hipLaunchKernelGGL((k_bf_tiled<T, O>), grid, dim3(256), 0, s, g, buf, rgb, byte);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    const dim3 grid((g.W + 63) / 64, (g.H + 3) / 4);
-    hipLaunchKernelGGL((k_bf_green<T>), grid, dim3(256), 0, s, g, buf, ws);
-    hipLaunchKernelGGL((k_bf_final<T, O>), grid, dim3(256), 0, s, g, buf, (const float *)ws, rgb, byte);
+int launch_bayerfast(Img g, const T *buf, O *rgb, int byte, hipStream_t s) {
+    const dim3 grid((g.W + BFT_W - 1) / BFT_W, (g.H + BFT_H - 1) / BFT_H);
+    // pair stores: even width and an output aligned to the pair size
+    const int vec = (g.W % 2 == 0) && (reinterpret_cast<uintptr_t>(rgb) % (2 * sizeof(O)) == 0);
+    hipLaunchKernelGGL((k_bf_pairs<T, O>), grid, dim3(256), 0, s, g, buf, rgb, byte, vec);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-template int launch_bayerfast<float, float>(Img, const float *, float *, int, float *, hipStream_t);
-template int launch_bayerfast<uint16_t, uint16_t>(Img, const uint16_t *, uint16_t *, int, float *, hipStream_t);
+template int launch_bayerfast<float, float>(Img, const float *, float *, int, hipStream_t);
+template int launch_bayerfast<uint16_t, uint16_t>(Img, const uint16_t *, uint16_t *, int, hipStream_t);
 
-// ---------------------------------------------------------------- fused RCD
-// The whole RCD pipeline (k_prep .. k_final above, same expressions in the
-// same order, so the result is bitwise that of the multi-pass kernels) for a
-// TX x TY output tile in one workgroup: every intermediate plane lives in LDS
-// over the tile plus the halo the later steps read (cfa +10, V/H +7, VH +6,
-// LP +7, P/Q +5, G +5, PQ +4, R/B +3), recomputed on the overlap instead of
-// round-tripping 8 full planes through HBM.  HBM traffic: one read of the
-// CFA frame (plus its halo) and one write of the three output planes.
-struct Pl {
-    float *d;
-    int x0, y0, pw;   // global coordinates of element [0][0]; row pitch
-    __device__ __forceinline__ float at(int x, int y) const { return d[(y - y0) * pw + (x - x0)]; }
-};
-
-template <int TX, int TY>
-struct RcdLayout {
-    static constexpr int CFA = 10, VHH = 7, VHD = 6, LPH = 7, PQH = 5, PQD = 4, GH = 5, RBH = 3;
-    static constexpr int w(int h) { return TX + 2 * h; }
-    static constexpr int h(int hh) { return TY + 2 * hh; }
-    static constexpr int n(int hh) { return w(hh) * h(hh); }
-    // LDS plan: [cfa][V -> P -> R][H -> Q -> B][VH][LP][PQ][G]
-    static constexpr int o_cfa = 0;
-    static constexpr int o_a = o_cfa + n(CFA);
-    static constexpr int o_b = o_a + n(VHH);
-    static constexpr int o_vh = o_b + n(VHH);
-    static constexpr int o_lp = o_vh + n(VHD);
-    static constexpr int o_pq = o_lp + n(LPH);
-    static constexpr int o_g = o_pq + n(PQD);
-    static constexpr int total = o_g + n(GH);
-};
-
-template <int TX, int TY>
-size_t rcd_lds_bytes() { return sizeof(float) * RcdLayout<TX, TY>::total; }
-
-#define RCD_REGION(HALO)                                                         \
-    for (int i_ = threadIdx.x; i_ < L::n(HALO); i_ += blockDim.x) {              \
-        const int ly_ = i_ / L::w(HALO), lx_ = i_ - ly_ * L::w(HALO);            \
-        const int x = X0 - (HALO) + lx_, y = Y0 - (HALO) + ly_;                  \
-        const bool in_img = x >= 0 && y >= 0 && x < g.W && y < g.H;
-
-#define RCD_END }
-
-template <int TX, int TY, class T, class O>
-__global__ __launch_bounds__(512) void k_rcd_fused(Img g, const T *buf, O *rgb, int byte) {
-    using L = RcdLayout<TX, TY>;
-    extern __shared__ float lds[];
-    const int X0 = blockIdx.x * TX, Y0 = blockIdx.y * TY;
-    const int W = g.W;
-    const Pl cfa{lds + L::o_cfa, X0 - L::CFA, Y0 - L::CFA, L::w(L::CFA)};
-    const Pl V{lds + L::o_a, X0 - L::VHH, Y0 - L::VHH, L::w(L::VHH)};
-    const Pl Hh{lds + L::o_b, X0 - L::VHH, Y0 - L::VHH, L::w(L::VHH)};
-    const Pl VH{lds + L::o_vh, X0 - L::VHD, Y0 - L::VHD, L::w(L::VHD)};
-    const Pl LP{lds + L::o_lp, X0 - L::LPH, Y0 - L::LPH, L::w(L::LPH)};
-    const Pl P{lds + L::o_a, X0 - L::PQH, Y0 - L::PQH, L::w(L::PQH)};
-    const Pl Q{lds + L::o_b, X0 - L::PQH, Y0 - L::PQH, L::w(L::PQH)};
-    const Pl PQ{lds + L::o_pq, X0 - L::PQD, Y0 - L::PQD, L::w(L::PQD)};
-    const Pl G{lds + L::o_g, X0 - L::GH, Y0 - L::GH, L::w(L::GH)};
-    const Pl R{lds + L::o_a, X0 - L::RBH, Y0 - L::RBH, L::w(L::RBH)};
-    const Pl B{lds + L::o_b, X0 - L::RBH, Y0 - L::RBH, L::w(L::RBH)};
-    float mn, factor;
-    norm_consts(g, mn, factor);
-
-    // k_prep
-    RCD_REGION(L::CFA)
-        float v = 0.f;
-        if (in_img) {
-            const float raw = (ld(buf, (long long)y * W + x) - mn) * factor;
-            const float t = raw / SCALE;
-            v = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-        }
-        cfa.d[i_] = v;
-    RCD_END
-    __syncthreads();
-    // k_hv
-    RCD_REGION(L::VHH)
-        float v = 0.f, h = 0.f;
-        if (in_img) {
-            if (y >= 3 && y < g.H - 3 && x >= 4 && x < g.W - 4)
-                v = hpf2(cfa.at(x, y - 3), cfa.at(x, y - 2), cfa.at(x, y - 1), cfa.at(x, y), cfa.at(x, y + 1),
-                         cfa.at(x, y + 2), cfa.at(x, y + 3));
-            if (y >= 4 && y < g.H - 4 && x >= 3 && x < g.W - 3)
-                h = hpf2(cfa.at(x - 3, y), cfa.at(x - 2, y), cfa.at(x - 1, y), cfa.at(x, y), cfa.at(x + 1, y),
-                         cfa.at(x + 2, y), cfa.at(x + 3, y));
-        }
-        V.d[i_] = v;
-        Hh.d[i_] = h;
-    RCD_END
-    __syncthreads();
-    // k_dir: VH_Dir, then (V / H dead) low pass and diagonal high-pass
-    RCD_REGION(L::VHD)
-        float vh = 0.f;
-        if (in_img && inr(g, y, x, 4)) {
-            const float vs = fmaxf(EPSSQ, (V.at(x, y - 1) + V.at(x, y)) + V.at(x, y + 1));
-            const float hs = fmaxf(EPSSQ, (Hh.at(x - 1, y) + Hh.at(x, y)) + Hh.at(x + 1, y));
-            vh = vs / (vs + hs);
-        }
-        VH.d[i_] = vh;
-    RCD_END
-    RCD_REGION(L::LPH)
-        float lp = 0.f;
-        if (in_img && fc(g, y, x) != 1 && inr(g, y, x, 2)) {
-            lp = cfa.at(x, y) + 0.5f * (((cfa.at(x, y - 1) + cfa.at(x, y + 1)) + cfa.at(x - 1, y)) + cfa.at(x + 1, y));
-            lp = lp + 0.25f * (((cfa.at(x - 1, y - 1) + cfa.at(x + 1, y - 1)) + cfa.at(x - 1, y + 1)) +
-                               cfa.at(x + 1, y + 1));
-        }
-        LP.d[i_] = lp;
-    RCD_END
-    __syncthreads();
-    RCD_REGION(L::PQH)
-        float pp = 0.f, qq = 0.f;
-        if (in_img && fc(g, y, x) != 1 && inr(g, y, x, 3)) {
-            pp = hpf2(cfa.at(x - 3, y - 3), cfa.at(x - 2, y - 2), cfa.at(x - 1, y - 1), cfa.at(x, y),
-                      cfa.at(x + 1, y + 1), cfa.at(x + 2, y + 2), cfa.at(x + 3, y + 3));
-            qq = hpf2(cfa.at(x + 3, y - 3), cfa.at(x + 2, y - 2), cfa.at(x + 1, y - 1), cfa.at(x, y),
-                      cfa.at(x - 1, y + 1), cfa.at(x - 2, y + 2), cfa.at(x - 3, y + 3));
-        }
-        P.d[i_] = pp;
-        Q.d[i_] = qq;
-    RCD_END
-    __syncthreads();
-    // k_green
-    RCD_REGION(L::GH)
-        float gv = 0.f;
-        if (in_img) {
-            const float c0 = cfa.at(x, y);
-            if (fc(g, y, x) == 1) {
-                gv = c0;
-            } else if (inr(g, y, x, 4)) {
-                const float n1 = cfa.at(x, y - 1), s1 = cfa.at(x, y + 1), w1 = cfa.at(x - 1, y), e1 = cfa.at(x + 1, y);
-                const float n2 = cfa.at(x, y - 2), s2 = cfa.at(x, y + 2), w2 = cfa.at(x - 2, y), e2 = cfa.at(x + 2, y);
-                const float N_Grad = (EPS + (fabsf(n1 - s1) + fabsf(c0 - n2))) +
-                                     (fabsf(n1 - cfa.at(x, y - 3)) + fabsf(n2 - cfa.at(x, y - 4)));
-                const float S_Grad = (EPS + (fabsf(n1 - s1) + fabsf(c0 - s2))) +
-                                     (fabsf(s1 - cfa.at(x, y + 3)) + fabsf(s2 - cfa.at(x, y + 4)));
-                const float W_Grad = (EPS + (fabsf(w1 - e1) + fabsf(c0 - w2))) +
-                                     (fabsf(w1 - cfa.at(x - 3, y)) + fabsf(w2 - cfa.at(x - 4, y)));
-                const float E_Grad = (EPS + (fabsf(w1 - e1) + fabsf(c0 - e2))) +
-                                     (fabsf(e1 - cfa.at(x + 3, y)) + fabsf(e2 - cfa.at(x + 4, y)));
-                const float lpi = LP.at(x, y);
-                const float l2 = lpi + lpi;
-                const float N_Est = n1 * l2 / ((EPS + lpi) + LP.at(x, y - 2));
-                const float S_Est = s1 * l2 / ((EPS + lpi) + LP.at(x, y + 2));
-                const float W_Est = w1 * l2 / ((EPS + lpi) + LP.at(x - 2, y));
-                const float E_Est = e1 * l2 / ((EPS + lpi) + LP.at(x + 2, y));
-                const float V_Est = (S_Grad * N_Est + N_Grad * S_Est) / (N_Grad + S_Grad);
-                const float H_Est = (W_Grad * E_Est + E_Grad * W_Est) / (E_Grad + W_Grad);
-                const float nb = 0.25f * ((VH.at(x - 1, y - 1) + VH.at(x + 1, y - 1)) +
-                                          (VH.at(x - 1, y + 1) + VH.at(x + 1, y + 1)));
-                const float d = disc(VH.at(x, y), nb);
-                gv = d * (H_Est - V_Est) + V_Est;
-            }
-        }
-        G.d[i_] = gv;
-    RCD_END
-    // k_pq writes the PQ ratio into the low-pass buffer only at non-green
-    // interior sites: elsewhere that buffer still holds LP
-    RCD_REGION(L::PQD)
-        float v = 0.f;
-        if (in_img) {
-            if (fc(g, y, x) != 1 && inr(g, y, x, 4)) {
-                const float ps = fmaxf(EPSSQ, (P.at(x - 1, y - 1) + P.at(x, y)) + P.at(x + 1, y + 1));
-                const float qs = fmaxf(EPSSQ, (Q.at(x + 1, y - 1) + Q.at(x, y)) + Q.at(x - 1, y + 1));
-                v = ps / (ps + qs);
-            } else {
-                v = LP.at(x, y);
-            }
-        }
-        PQ.d[i_] = v;
-    RCD_END
-    __syncthreads();
-    // k_rb_sites (P / Q dead: R / B take their buffers)
-    RCD_REGION(L::RBH)
-        float r = 0.f, b = 0.f;
-        if (in_img) {
-            const int col = fc(g, y, x);
-            const float c0 = cfa.at(x, y);
-            r = col == 0 ? c0 : 0.f;
-            b = col == 2 ? c0 : 0.f;
-            if (col != 1 && inr(g, y, x, 4)) {
-                const float nb = 0.25f * (((PQ.at(x - 1, y - 1) + PQ.at(x + 1, y - 1)) + PQ.at(x - 1, y + 1)) +
-                                          PQ.at(x + 1, y + 1));
-                const float d = disc(PQ.at(x, y), nb);
-                const float NW = cfa.at(x - 1, y - 1), NE = cfa.at(x + 1, y - 1), SW = cfa.at(x - 1, y + 1),
-                            SE = cfa.at(x + 1, y + 1);
-                const float g0 = G.at(x, y);
-                const float NW_Grad = ((EPS + fabsf(NW - SE)) + fabsf(NW - cfa.at(x - 3, y - 3))) + fabsf(g0 - G.at(x - 2, y - 2));
-                const float NE_Grad = ((EPS + fabsf(NE - SW)) + fabsf(NE - cfa.at(x + 3, y - 3))) + fabsf(g0 - G.at(x + 2, y - 2));
-                const float SW_Grad = ((EPS + fabsf(NE - SW)) + fabsf(SW - cfa.at(x - 3, y + 3))) + fabsf(g0 - G.at(x - 2, y + 2));
-                const float SE_Grad = ((EPS + fabsf(NW - SE)) + fabsf(SE - cfa.at(x + 3, y + 3))) + fabsf(g0 - G.at(x + 2, y + 2));
-                const float NW_Est = NW - G.at(x - 1, y - 1);
-                const float NE_Est = NE - G.at(x + 1, y - 1);
-                const float SW_Est = SW - G.at(x - 1, y + 1);
-                const float SE_Est = SE - G.at(x + 1, y + 1);
-                const float P_Est = (NW_Grad * SE_Est + SE_Grad * NW_Est) / (NW_Grad + SE_Grad);
-                const float Q_Est = (NE_Grad * SW_Est + SW_Grad * NE_Est) / (NE_Grad + SW_Grad);
-                const float v = g0 + (d * (Q_Est - P_Est) + P_Est);
-                if (col == 2) r = v;     // interpolating colour 2 - col
-                else b = v;
-            }
-        }
-        R.d[i_] = r;
-        B.d[i_] = b;
-    RCD_END
-    __syncthreads();
-    // k_final
-    const float invfactor = (float)(1.0 / (double)factor);
-    const long long n = (long long)g.W * g.H;
-    RCD_REGION(0)
-        if (!in_img) continue;
-        float o[3];
-        if (!inr(g, y, x, BORDER)) {
-            border(g, buf, mn, factor, y, x, o);
-        } else {
-            float r = R.at(x, y), b = B.at(x, y);
-            const float g0 = G.at(x, y);
-            if (fc(g, y, x) == 1) {
-                const float nb = 0.25f * ((VH.at(x - 1, y - 1) + VH.at(x + 1, y - 1)) +
-                                          (VH.at(x - 1, y + 1) + VH.at(x + 1, y + 1)));
-                const float d = disc(VH.at(x, y), nb);
-                const float N1 = EPS + fabsf(g0 - G.at(x, y - 2));
-                const float S1 = EPS + fabsf(g0 - G.at(x, y + 2));
-                const float W1 = EPS + fabsf(g0 - G.at(x - 2, y));
-                const float E1 = EPS + fabsf(g0 - G.at(x + 2, y));
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    const Pl &pl = k == 0 ? R : B;
-                    const float SNabs = fabsf(pl.at(x, y - 1) - pl.at(x, y + 1));
-                    const float EWabs = fabsf(pl.at(x - 1, y) - pl.at(x + 1, y));
-                    const float N_Grad = (N1 + SNabs) + fabsf(pl.at(x, y - 1) - pl.at(x, y - 3));
-                    const float S_Grad = (S1 + SNabs) + fabsf(pl.at(x, y + 1) - pl.at(x, y + 3));
-                    const float W_Grad = (W1 + EWabs) + fabsf(pl.at(x - 1, y) - pl.at(x - 3, y));
-                    const float E_Grad = (E1 + EWabs) + fabsf(pl.at(x + 1, y) - pl.at(x + 3, y));
-                    const float N_Est = pl.at(x, y - 1) - G.at(x, y - 1);
-                    const float S_Est = pl.at(x, y + 1) - G.at(x, y + 1);
-                    const float W_Est = pl.at(x - 1, y) - G.at(x - 1, y);
-                    const float E_Est = pl.at(x + 1, y) - G.at(x + 1, y);
-                    const float V_Est = (N_Grad * S_Est + S_Grad * N_Est) / (N_Grad + S_Grad);
-                    const float H_Est = (E_Grad * W_Est + W_Grad * E_Est) / (E_Grad + W_Grad);
-                    const float v = g0 + (d * (H_Est - V_Est) + V_Est);
-                    if (k == 0) r = v;
-                    else b = v;
-                }
-            }
-            o[0] = fmaxf(0.f, r * SCALE);
-            o[1] = fmaxf(0.f, g0 * SCALE);
-            o[2] = fmaxf(0.f, b * SCALE);
-        }
-        const long long p = (long long)y * W + x;
-#pragma unroll
-        for (int k = 0; k < 3; k++) st(rgb, k * n + p, o[k] * invfactor + mn, byte);
-    RCD_END
-}
-
-template <int TX, int TY, class T, class O>
-int launch_rcd_fused(Img g, const T *buf, O *rgb, int byte, int threads, hipStream_t s) {
-    const size_t lds = rcd_lds_bytes<TX, TY>();
-    static bool configured = false;
-    if (!configured) {
-        if (hipFuncSetAttribute((const void *)k_rcd_fused<TX, TY, T, O>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return -1;
-        configured = true;
-    }
-    const dim3 grid((g.W + TX - 1) / TX, (g.H + TY - 1) / TY);
-    hipLaunchKernelGGL((k_rcd_fused<TX, TY, T, O>), grid, dim3(threads), lds, s, g, buf, rgb, byte);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// ------------------------------------------------------- two-kernel RCD
-// The fused kernel's halo (cfa +10) and LDS plan (98 KB at 64 x 32: one
-// workgroup per CU) cost more than the HBM round trips it saves.  Cut at the
-// narrowest point instead: k_rcd_a computes steps 1-4.1 over the tile and
-// writes G, VH and the PQ / LP plane (12 B/px); k_rcd_b reads them back with
-// the halos steps 4.2-4.3 need and writes the output.  HBM per pixel: 4 (raw,
-// each kernel) + 12 + 12 + 12 (output) = 44 B against the multi-pass
-// pipeline's ~8 planes written and re-read.  Same expressions in the same
-// order as k_prep .. k_final: bitwise the multi-pass result.
-template <int TX, int TY>
-struct RcdA {
-    static constexpr int CFA = 6, VHH = 2, VHD = 1, LPH = 2, PQH = 1;
-    static constexpr int w(int h) { return TX + 2 * h; }
-    static constexpr int h(int hh) { return TY + 2 * hh; }
-    static constexpr int n(int hh) { return w(hh) * h(hh); }
-    // [cfa][V -> P][H -> Q][VH][LP]
-    static constexpr int o_cfa = 0, o_a = n(CFA), o_b = o_a + n(VHH), o_vh = o_b + n(VHH), o_lp = o_vh + n(VHD);
-    static constexpr int total = o_lp + n(LPH);
-};
-template <int TX, int TY>
-struct RcdB {
-    static constexpr int CFA = 6, GH = 5, PQD = 4, RBH = 3, VHD = 1;
-    static constexpr int w(int h) { return TX + 2 * h; }
-    static constexpr int h(int hh) { return TY + 2 * hh; }
-    static constexpr int n(int hh) { return w(hh) * h(hh); }
-    static constexpr int o_cfa = 0, o_g = n(CFA), o_pq = o_g + n(GH), o_vh = o_pq + n(PQD), o_r = o_vh + n(VHD),
-                         o_b = o_r + n(RBH);
-    static constexpr int total = o_b + n(RBH);
-};
-
-template <int TX, int TY, class T>
-__global__ __launch_bounds__(256) void k_rcd_a(Img g, const T *buf, float *Gout, float *VHout, float *PQout) {
-    using L = RcdA<TX, TY>;
-    extern __shared__ float lds[];
-    const int X0 = blockIdx.x * TX, Y0 = blockIdx.y * TY;
-    const int W = g.W;
-    const Pl cfa{lds + L::o_cfa, X0 - L::CFA, Y0 - L::CFA, L::w(L::CFA)};
-    const Pl V{lds + L::o_a, X0 - L::VHH, Y0 - L::VHH, L::w(L::VHH)};
-    const Pl Hh{lds + L::o_b, X0 - L::VHH, Y0 - L::VHH, L::w(L::VHH)};
-    const Pl VH{lds + L::o_vh, X0 - L::VHD, Y0 - L::VHD, L::w(L::VHD)};
-    const Pl LP{lds + L::o_lp, X0 - L::LPH, Y0 - L::LPH, L::w(L::LPH)};
-    const Pl P{lds + L::o_a, X0 - L::PQH, Y0 - L::PQH, L::w(L::PQH)};
-    const Pl Q{lds + L::o_b, X0 - L::PQH, Y0 - L::PQH, L::w(L::PQH)};
-    float mn, factor;
-    norm_consts(g, mn, factor);
-    RCD_REGION(L::CFA)                                   // k_prep
-        float v = 0.f;
-        if (in_img) {
-            const float raw = (ld(buf, (long long)y * W + x) - mn) * factor;
-            const float t = raw / SCALE;
-            v = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-        }
-        cfa.d[i_] = v;
-    RCD_END
-    __syncthreads();
-    RCD_REGION(L::VHH)                                   // k_hv
-        float v = 0.f, h = 0.f;
-        if (in_img) {
-            if (y >= 3 && y < g.H - 3 && x >= 4 && x < g.W - 4)
-                v = hpf2(cfa.at(x, y - 3), cfa.at(x, y - 2), cfa.at(x, y - 1), cfa.at(x, y), cfa.at(x, y + 1),
-                         cfa.at(x, y + 2), cfa.at(x, y + 3));
-            if (y >= 4 && y < g.H - 4 && x >= 3 && x < g.W - 3)
-                h = hpf2(cfa.at(x - 3, y), cfa.at(x - 2, y), cfa.at(x - 1, y), cfa.at(x, y), cfa.at(x + 1, y),
-                         cfa.at(x + 2, y), cfa.at(x + 3, y));
-        }
-        V.d[i_] = v;
-        Hh.d[i_] = h;
-    RCD_END
-    __syncthreads();
-    RCD_REGION(L::VHD)                                   // k_dir: VH_Dir
-        float vh = 0.f;
-        if (in_img && inr(g, y, x, 4)) {
-            const float vs = fmaxf(EPSSQ, (V.at(x, y - 1) + V.at(x, y)) + V.at(x, y + 1));
-            const float hs = fmaxf(EPSSQ, (Hh.at(x - 1, y) + Hh.at(x, y)) + Hh.at(x + 1, y));
-            vh = vs / (vs + hs);
-        }
-        VH.d[i_] = vh;
-    RCD_END
-    RCD_REGION(L::LPH)                                   // low pass
-        float lp = 0.f;
-        if (in_img && fc(g, y, x) != 1 && inr(g, y, x, 2)) {
-            lp = cfa.at(x, y) + 0.5f * (((cfa.at(x, y - 1) + cfa.at(x, y + 1)) + cfa.at(x - 1, y)) + cfa.at(x + 1, y));
-            lp = lp + 0.25f * (((cfa.at(x - 1, y - 1) + cfa.at(x + 1, y - 1)) + cfa.at(x - 1, y + 1)) +
-                               cfa.at(x + 1, y + 1));
-        }
-        LP.d[i_] = lp;
-    RCD_END
-    __syncthreads();
-    RCD_REGION(L::PQH)                                   // diagonal high-pass (V / H dead)
-        float pp = 0.f, qq = 0.f;
-        if (in_img && fc(g, y, x) != 1 && inr(g, y, x, 3)) {
-            pp = hpf2(cfa.at(x - 3, y - 3), cfa.at(x - 2, y - 2), cfa.at(x - 1, y - 1), cfa.at(x, y),
-                      cfa.at(x + 1, y + 1), cfa.at(x + 2, y + 2), cfa.at(x + 3, y + 3));
-            qq = hpf2(cfa.at(x + 3, y - 3), cfa.at(x + 2, y - 2), cfa.at(x + 1, y - 1), cfa.at(x, y),
-                      cfa.at(x - 1, y + 1), cfa.at(x - 2, y + 2), cfa.at(x - 3, y + 3));
-        }
-        P.d[i_] = pp;
-        Q.d[i_] = qq;
-    RCD_END
-    __syncthreads();
-    RCD_REGION(0)                                        // k_green and k_pq over the tile
-        if (!in_img) continue;
-        float gv = 0.f;
-        const float c0 = cfa.at(x, y);
-        const bool green = fc(g, y, x) == 1;
-        if (green) {
-            gv = c0;
-        } else if (inr(g, y, x, 4)) {
-            const float n1 = cfa.at(x, y - 1), s1 = cfa.at(x, y + 1), w1 = cfa.at(x - 1, y), e1 = cfa.at(x + 1, y);
-            const float n2 = cfa.at(x, y - 2), s2 = cfa.at(x, y + 2), w2 = cfa.at(x - 2, y), e2 = cfa.at(x + 2, y);
-            const float N_Grad = (EPS + (fabsf(n1 - s1) + fabsf(c0 - n2))) +
-                                 (fabsf(n1 - cfa.at(x, y - 3)) + fabsf(n2 - cfa.at(x, y - 4)));
-            const float S_Grad = (EPS + (fabsf(n1 - s1) + fabsf(c0 - s2))) +
-                                 (fabsf(s1 - cfa.at(x, y + 3)) + fabsf(s2 - cfa.at(x, y + 4)));
-            const float W_Grad = (EPS + (fabsf(w1 - e1) + fabsf(c0 - w2))) +
-                                 (fabsf(w1 - cfa.at(x - 3, y)) + fabsf(w2 - cfa.at(x - 4, y)));
-            const float E_Grad = (EPS + (fabsf(w1 - e1) + fabsf(c0 - e2))) +
-                                 (fabsf(e1 - cfa.at(x + 3, y)) + fabsf(e2 - cfa.at(x + 4, y)));
-            const float lpi = LP.at(x, y);
-            const float l2 = lpi + lpi;
-            const float N_Est = n1 * l2 / ((EPS + lpi) + LP.at(x, y - 2));
-            const float S_Est = s1 * l2 / ((EPS + lpi) + LP.at(x, y + 2));
-            const float W_Est = w1 * l2 / ((EPS + lpi) + LP.at(x - 2, y));
-            const float E_Est = e1 * l2 / ((EPS + lpi) + LP.at(x + 2, y));
-            const float V_Est = (S_Grad * N_Est + N_Grad * S_Est) / (N_Grad + S_Grad);
-            const float H_Est = (W_Grad * E_Est + E_Grad * W_Est) / (E_Grad + W_Grad);
-            const float nb = 0.25f * ((VH.at(x - 1, y - 1) + VH.at(x + 1, y - 1)) +
-                                      (VH.at(x - 1, y + 1) + VH.at(x + 1, y + 1)));
-            const float d = disc(VH.at(x, y), nb);
-            gv = d * (H_Est - V_Est) + V_Est;
-        }
-        float pq;
-        if (!green && inr(g, y, x, 4)) {
-            const float ps = fmaxf(EPSSQ, (P.at(x - 1, y - 1) + P.at(x, y)) + P.at(x + 1, y + 1));
-            const float qs = fmaxf(EPSSQ, (Q.at(x + 1, y - 1) + Q.at(x, y)) + Q.at(x - 1, y + 1));
-            pq = ps / (ps + qs);
-        } else {
-            pq = LP.at(x, y);
-        }
-        const long long p = (long long)y * W + x;
-        Gout[p] = gv;
-        VHout[p] = VH.at(x, y);
-        PQout[p] = pq;
-    RCD_END
-}
-
-template <int TX, int TY, class T, class O>
-__global__ __launch_bounds__(256) void k_rcd_b(Img g, const T *buf, const float *Gin, const float *VHin,
-                                               const float *PQin, O *rgb, int byte) {
-    using L = RcdB<TX, TY>;
-    extern __shared__ float lds[];
-    const int X0 = blockIdx.x * TX, Y0 = blockIdx.y * TY;
-    const int W = g.W;
-    const Pl cfa{lds + L::o_cfa, X0 - L::CFA, Y0 - L::CFA, L::w(L::CFA)};
-    const Pl G{lds + L::o_g, X0 - L::GH, Y0 - L::GH, L::w(L::GH)};
-    const Pl PQ{lds + L::o_pq, X0 - L::PQD, Y0 - L::PQD, L::w(L::PQD)};
-    const Pl VH{lds + L::o_vh, X0 - L::VHD, Y0 - L::VHD, L::w(L::VHD)};
-    const Pl R{lds + L::o_r, X0 - L::RBH, Y0 - L::RBH, L::w(L::RBH)};
-    const Pl B{lds + L::o_b, X0 - L::RBH, Y0 - L::RBH, L::w(L::RBH)};
-    float mn, factor;
-    norm_consts(g, mn, factor);
-    RCD_REGION(L::CFA)
-        float v = 0.f;
-        if (in_img) {
-            const float raw = (ld(buf, (long long)y * W + x) - mn) * factor;
-            const float t = raw / SCALE;
-            v = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-        }
-        cfa.d[i_] = v;
-    RCD_END
-    RCD_REGION(L::GH)
-        G.d[i_] = in_img ? Gin[(long long)y * W + x] : 0.f;
-    RCD_END
-    RCD_REGION(L::PQD)
-        PQ.d[i_] = in_img ? PQin[(long long)y * W + x] : 0.f;
-    RCD_END
-    RCD_REGION(L::VHD)
-        VH.d[i_] = in_img ? VHin[(long long)y * W + x] : 0.f;
-    RCD_END
-    __syncthreads();
-    RCD_REGION(L::RBH)                                   // k_rb_sites
-        float r = 0.f, b = 0.f;
-        if (in_img) {
-            const int col = fc(g, y, x);
-            const float c0 = cfa.at(x, y);
-            r = col == 0 ? c0 : 0.f;
-            b = col == 2 ? c0 : 0.f;
-            if (col != 1 && inr(g, y, x, 4)) {
-                const float nb = 0.25f * (((PQ.at(x - 1, y - 1) + PQ.at(x + 1, y - 1)) + PQ.at(x - 1, y + 1)) +
-                                          PQ.at(x + 1, y + 1));
-                const float d = disc(PQ.at(x, y), nb);
-                const float NW = cfa.at(x - 1, y - 1), NE = cfa.at(x + 1, y - 1), SW = cfa.at(x - 1, y + 1),
-                            SE = cfa.at(x + 1, y + 1);
-                const float g0 = G.at(x, y);
-                const float NW_Grad = ((EPS + fabsf(NW - SE)) + fabsf(NW - cfa.at(x - 3, y - 3))) + fabsf(g0 - G.at(x - 2, y - 2));
-                const float NE_Grad = ((EPS + fabsf(NE - SW)) + fabsf(NE - cfa.at(x + 3, y - 3))) + fabsf(g0 - G.at(x + 2, y - 2));
-                const float SW_Grad = ((EPS + fabsf(NE - SW)) + fabsf(SW - cfa.at(x - 3, y + 3))) + fabsf(g0 - G.at(x - 2, y + 2));
-                const float SE_Grad = ((EPS + fabsf(NW - SE)) + fabsf(SE - cfa.at(x + 3, y + 3))) + fabsf(g0 - G.at(x + 2, y + 2));
-                const float NW_Est = NW - G.at(x - 1, y - 1);
-                const float NE_Est = NE - G.at(x + 1, y - 1);
-                const float SW_Est = SW - G.at(x - 1, y + 1);
-                const float SE_Est = SE - G.at(x + 1, y + 1);
-                const float P_Est = (NW_Grad * SE_Est + SE_Grad * NW_Est) / (NW_Grad + SE_Grad);
-                const float Q_Est = (NE_Grad * SW_Est + SW_Grad * NE_Est) / (NE_Grad + SW_Grad);
-                const float v = g0 + (d * (Q_Est - P_Est) + P_Est);
-                if (col == 2) r = v;
-                else b = v;
-            }
-        }
-        R.d[i_] = r;
-        B.d[i_] = b;
-    RCD_END
-    __syncthreads();
-    const float invfactor = (float)(1.0 / (double)factor);
-    const long long n = (long long)g.W * g.H;
-    RCD_REGION(0)                                        // k_final
-        if (!in_img) continue;
-        float o[3];
-        if (!inr(g, y, x, BORDER)) {
-            border(g, buf, mn, factor, y, x, o);
-        } else {
-            float r = R.at(x, y), b = B.at(x, y);
-            const float g0 = G.at(x, y);
-            if (fc(g, y, x) == 1) {
-                const float nb = 0.25f * ((VH.at(x - 1, y - 1) + VH.at(x + 1, y - 1)) +
-                                          (VH.at(x - 1, y + 1) + VH.at(x + 1, y + 1)));
-                const float d = disc(VH.at(x, y), nb);
-                const float N1 = EPS + fabsf(g0 - G.at(x, y - 2));
-                const float S1 = EPS + fabsf(g0 - G.at(x, y + 2));
-                const float W1 = EPS + fabsf(g0 - G.at(x - 2, y));
-                const float E1 = EPS + fabsf(g0 - G.at(x + 2, y));
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    const Pl &pl = k == 0 ? R : B;
-                    const float SNabs = fabsf(pl.at(x, y - 1) - pl.at(x, y + 1));
-                    const float EWabs = fabsf(pl.at(x - 1, y) - pl.at(x + 1, y));
-                    const float N_Grad = (N1 + SNabs) + fabsf(pl.at(x, y - 1) - pl.at(x, y - 3));
-                    const float S_Grad = (S1 + SNabs) + fabsf(pl.at(x, y + 1) - pl.at(x, y + 3));
-                    const float W_Grad = (W1 + EWabs) + fabsf(pl.at(x - 1, y) - pl.at(x - 3, y));
-                    const float E_Grad = (E1 + EWabs) + fabsf(pl.at(x + 1, y) - pl.at(x + 3, y));
-                    const float N_Est = pl.at(x, y - 1) - G.at(x, y - 1);
-                    const float S_Est = pl.at(x, y + 1) - G.at(x, y + 1);
-                    const float W_Est = pl.at(x - 1, y) - G.at(x - 1, y);
-                    const float E_Est = pl.at(x + 1, y) - G.at(x + 1, y);
-                    const float V_Est = (N_Grad * S_Est + S_Grad * N_Est) / (N_Grad + S_Grad);
-                    const float H_Est = (E_Grad * W_Est + W_Grad * E_Est) / (E_Grad + W_Grad);
-                    const float v = g0 + (d * (H_Est - V_Est) + V_Est);
-                    if (k == 0) r = v;
-                    else b = v;
-                }
-            }
-            o[0] = fmaxf(0.f, r * SCALE);
-            o[1] = fmaxf(0.f, g0 * SCALE);
-            o[2] = fmaxf(0.f, b * SCALE);
-        }
-        const long long p = (long long)y * W + x;
-#pragma unroll
-        for (int k = 0; k < 3; k++) st(rgb, k * n + p, o[k] * invfactor + mn, byte);
-    RCD_END
-}
-
-template <int TX, int TY, class T, class O>
-int launch_rcd_split(Img g, const T *buf, O *rgb, int byte, float *ws, hipStream_t s) {
-    const long long n = (long long)g.W * g.H;
-    float *G = ws, *VH = ws + n, *PQ = ws + 2 * n;
-    const size_t la = sizeof(float) * RcdA<TX, TY>::total, lb = sizeof(float) * RcdB<TX, TY>::total;
-    static bool configured = false;
-    if (!configured) {
-        if (hipFuncSetAttribute((const void *)k_rcd_a<TX, TY, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)la) != hipSuccess ||
-            hipFuncSetAttribute((const void *)k_rcd_b<TX, TY, T, O>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lb) != hipSuccess)
-            return -1;
-        configured = true;
-    }
-    const dim3 grid((g.W + TX - 1) / TX, (g.H + TY - 1) / TY);
-    hipLaunchKernelGGL((k_rcd_a<TX, TY, T>), grid, dim3(256), la, s, g, buf, G, VH, PQ);
-    hipLaunchKernelGGL((k_rcd_b<TX, TY, T, O>), grid, dim3(256), lb, s, g, buf, G, VH, PQ, rgb, byte);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// tile variants (A/B knob SGPU_RCD_FUSED: 1 = 64x32 / 512 threads, 2 = 32x32 / 256)
-template <class T, class O>
-int launch_rcd(Img g, const T *buf, O *rgb, int byte, int variant, hipStream_t s) {
-    if (variant == 1) return launch_rcd_fused<32, 32>(g, buf, rgb, byte, 256, s);
-    return launch_rcd_fused<64, 32>(g, buf, rgb, byte, 512, s);
-}
-
-// the multi-pass pipeline (workspace: 8 planes of W x H floats)
+// the RCD pipeline, a few steps per kernel over the whole image (workspace: 7
+// planes of W x H floats): 0.90 ms per 6000x4000 frame.  The LDS-tiled forms
+// it was measured against, all bitwise equal to it, lost (round 4, round 6):
+// the whole pipeline in one kernel needs a 10-pixel CFA halo and 98 KB of
+// LDS at 64 x 32 tiles, one workgroup per CU (1.26 ms); cut in two at the
+// narrowest point (steps 1-4.1 | 4.2-4.3, 2.75x the traffic floor against
+// ~16x) it still took 1.32 ms.
 template <class T, class O>
 int launch_rcd_multipass(Img g, const T *buf, O *rgb, int byte, float *ws, hipStream_t s) {
     const long long n = (long long)g.W * g.H;
-    float *cfa = ws, *V = ws + n, *Hh = ws + 2 * n, *VH = ws + 3 * n, *LP = ws + 4 * n, *P = ws + 5 * n,
-          *Q = ws + 6 * n, *G = ws + 7 * n;
+    float *cfa = ws, *R = ws + n, *B = ws + 2 * n, *VH = ws + 3 * n, *LP = ws + 4 * n, *PQ = ws + 5 * n,
+          *G = ws + 6 * n;
     const dim3 grid((g.W + 63) / 64, (g.H + 3) / 4), blk(256);
     hipLaunchKernelGGL(k_prep<T>, grid, blk, 0, s, g, buf, cfa);
-    // SGPU_RCD_DIRPQ=0: the three-kernel form of steps 1.1-2 and 4.1 (A/B)
-    static const bool dirpq = !std::getenv("SGPU_RCD_DIRPQ") || std::atoi(std::getenv("SGPU_RCD_DIRPQ")) != 0;
-    if (dirpq) {
-        // V / Hh hold the red / blue site planes, P the PQ ratio
-        hipLaunchKernelGGL(k_dir_pq, grid, blk, 0, s, g, cfa, VH, LP, P);
-        hipLaunchKernelGGL(k_green, grid, blk, 0, s, g, cfa, VH, LP, G);
-        hipLaunchKernelGGL(k_rb_sites, grid, blk, 0, s, g, cfa, G, P, V, Hh);
-        hipLaunchKernelGGL((k_final<T, O>), grid, blk, 0, s, g, buf, G, VH, V, Hh, rgb, byte);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    hipLaunchKernelGGL(k_hv, grid, blk, 0, s, g, cfa, V, Hh);
-    hipLaunchKernelGGL(k_dir, grid, blk, 0, s, g, cfa, V, Hh, VH, LP, P, Q);
+    hipLaunchKernelGGL(k_dir_pq, grid, blk, 0, s, g, cfa, VH, LP, PQ);
     hipLaunchKernelGGL(k_green, grid, blk, 0, s, g, cfa, VH, LP, G);
-    hipLaunchKernelGGL(k_pq, grid, blk, 0, s, g, P, Q, LP);
-    // V / Hh are dead after k_dir: they hold the red / blue site planes
-    hipLaunchKernelGGL(k_rb_sites, grid, blk, 0, s, g, cfa, G, LP, V, Hh);
-    hipLaunchKernelGGL((k_final<T, O>), grid, blk, 0, s, g, buf, G, VH, V, Hh, rgb, byte);
+    hipLaunchKernelGGL(k_rb_sites, grid, blk, 0, s, g, cfa, G, PQ, R, B);
+    hipLaunchKernelGGL((k_final<T, O>), grid, blk, 0, s, g, buf, G, VH, R, B, rgb, byte);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-
-template int launch_rcd_split<64, 32, float, float>(Img, const float *, float *, int, float *, hipStream_t);
-template int launch_rcd_split<64, 32, uint16_t, uint16_t>(Img, const uint16_t *, uint16_t *, int, float *, hipStream_t);
-template int launch_rcd<float, float>(Img, const float *, float *, int, int, hipStream_t);
-template int launch_rcd<uint16_t, uint16_t>(Img, const uint16_t *, uint16_t *, int, int, hipStream_t);
 template int launch_rcd_multipass<float, float>(Img, const float *, float *, int, float *, hipStream_t);
 template int launch_rcd_multipass<uint16_t, uint16_t>(Img, const uint16_t *, uint16_t *, int, float *, hipStream_t);
 

@@ -7,12 +7,12 @@
 //   c = IFFT2(C), unnormalised           (:257)
 //   shift = first strict argmax of Re c (:259-265), wrapped to +-S/2 (:266-273)
 // The 2-D transforms are row FFTs in LDS on the half spectrum (real input
-// and output, see k_rows_real2_fwd) whose results are stored straight into the
-// column-major layout of the column pass (k_rows_real2_fwd_t /
-// k_rows_c2r2_argmax_t; the tiled transpose kernel is the A/B form), batched
-// over frames; the cross-power product is fused into the load of the first
-// inverse pass and the argmax into the last one (the correlation surface is
-// never written back).
+// and output, see k_rows_real2_fwd_t) whose results are stored straight into
+// the column-major layout of the column pass (k_rows_real2_fwd_t /
+// k_rows_c2r2_argmax_t), batched over frames; a frame's forward and inverse
+// column transforms and the cross-power product between them are one LDS pass
+// (k_cols_fwd_xpow_bwd), and the argmax is fused into the last inverse pass
+// (the correlation surface is never written back).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fft_lds.h"
@@ -98,8 +98,9 @@ __device__ __forceinline__ float sel_sample(const uint16_t *f, long long stride,
     return cfa.dim == 0 ? (float)f[(long long)row * stride + col] : nongreen16(f, stride, n, n, row, col, cfa);
 }
 
-// rows of the real selection -> complex row spectra.  grid (S, batch)
-// `plane`: elements per batch plane (n*n full spectra, nh*n half spectra)
+// forward transform of the rows of `data` in place (the reference spectrum's
+// column pass: its rows are the columns of the half spectrum).  grid (rows,
+// batch); `plane`: elements per batch plane
 __global__ __launch_bounds__(fft::kThreads) void k_rows_fwd(Plan pl, float2 *data, long long plane) {
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     const int n = pl.n;
@@ -111,45 +112,20 @@ __global__ __launch_bounds__(fft::kThreads) void k_rows_fwd(Plan pl, float2 *dat
     for (int i = threadIdx.x; i < n; i += blockDim.x) d[i] = r[i];
 }
 
-// cross power Fref . conj(F) then backward row transform, in place.
-__global__ __launch_bounds__(fft::kThreads) void k_rows_xpow_bwd(Plan pl, const float2 *fref, float2 *data,
-                                                                 long long plane) {
-    extern __shared__ __attribute__((aligned(16))) float2 lds[];
-    const int n = pl.n;
-    float2 *a = lds, *b = lds + n;
-    float2 *d = data + (long long)blockIdx.y * plane + (long long)blockIdx.x * n;
-    const float2 *rr = fref + (long long)blockIdx.x * n;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float2 x = rr[i], y = d[i];
-        // in[x] * conjf(out2[x])  (shift_methods.c:254)
-        a[i] = make_float2(x.x * y.x + x.y * y.y, x.y * y.x - x.x * y.y);
-    }
-    __syncthreads();
-    float2 *r = fft::run<+1, true>(a, b, pl);
-    for (int i = threadIdx.x; i < n; i += blockDim.x) d[i] = r[i];
-}
-
 // column pass of a frame, fused: forward transform, cross power with the
 // reference's (transposed) spectrum, backward transform -- the same values
-// as k_rows_fwd followed by k_rows_xpow_bwd without the plane's HBM round
-// trip between them.
-// remap: the frames of one column run next to each other, on one XCD (the
-// dispatcher deals consecutive workgroups round-robin over the 8 XCDs, each
-// with its own L2), so the reference spectrum's column is read from HBM once
-// per batch instead of once per frame (32 x 64 MB per batch at S = 4000).
+// as two separate column passes without the plane's HBM round trip between
+// them.  grid (nh, batch) in the dispatcher's order: numbering the workgroups
+// so that the frames of one column run next to each other on one XCD (to
+// read the reference's column from HBM once per batch, not once per frame)
+// gained nothing (28.84-28.94 against 28.93-28.94 ms for dft100: the
+// spectrum's re-reads already hit the MALL).
 __global__ __launch_bounds__(fft::kThreads) void k_cols_fwd_xpow_bwd(Plan pl, const float2 *fref, float2 *data,
-                                                                     long long plane, int remap) {
+                                                                     long long plane) {
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     const int n = pl.n;
     float2 *a = lds, *b = lds + n;
-    int col = blockIdx.x, frame = blockIdx.y;
-    if (remap) {
-        const unsigned nbf = gridDim.y, total = gridDim.x * gridDim.y;
-        const unsigned L = blockIdx.y * gridDim.x + blockIdx.x;
-        const unsigned w = (total % 8u == 0u) ? (L % 8u) * (total / 8u) + L / 8u : L;   // XCD-contiguous ranges
-        col = (int)(w / nbf);
-        frame = (int)(w % nbf);
-    }
+    const int col = blockIdx.x, frame = blockIdx.y;
     float2 *d = data + (long long)frame * plane + (long long)col * n;
     for (int i = threadIdx.x; i < n; i += blockDim.x) a[i] = d[i];
     __syncthreads();
@@ -165,9 +141,6 @@ __global__ __launch_bounds__(fft::kThreads) void k_cols_fwd_xpow_bwd(Plan pl, co
     for (int i = threadIdx.x; i < n; i += blockDim.x) d[i] = r[i];
 }
 
-// last backward row transform + first-max argmax of the real part.
-// best[frame] = (ord(value) << 32) | ~index: atomicMax keeps the largest
-// value and, among equal values, the smallest row-major index.
 // ---------------------------------------------------------------- half spectrum
 // The image and the correlation surface are real, so only the half spectrum
 // kx in [0, n/2] is carried through the column passes (nh = n/2 + 1 columns):
@@ -177,34 +150,6 @@ __global__ __launch_bounds__(fft::kThreads) void k_cols_fwd_xpow_bwd(Plan pl, co
 // extension) so one complex inverse yields both real correlation rows.  Half
 // the column work and traffic of the full complex pipeline; the integer
 // argmax is what parity is pinned on (FFT bitwise parity unpinned).
-
-// rows 2j, 2j+1 of a frame -> half spectra rows 2j, 2j+1 (nh each, row pitch nh)
-// T: float selections, or WORD ones (DATA_USHORT sequences: (float)data,
-// after interpolate_nongreen_ushort for CFA frames)
-template <class T>
-__global__ __launch_bounds__(fft::kThreads) void k_rows_real2_fwd(Plan pl, const T *src,
-                                                                  long long row_stride,
-                                                                  long long frame_stride, float2 *dst,
-                                                                  fft::Cfa cfa) {
-    extern __shared__ __attribute__((aligned(16))) float2 lds[];
-    const int n = pl.n, nh = n / 2 + 1;
-    float2 *a = lds, *b = lds + n;
-    const T *f = src + blockIdx.y * frame_stride;
-    const int r0 = 2 * blockIdx.x, r1 = r0 + 1;
-    const bool has1 = r1 < n;
-    for (int i = threadIdx.x; i < n; i += blockDim.x)
-        a[i] = make_float2(sel_sample(f, row_stride, n, r0, i, cfa),
-                           has1 ? sel_sample(f, row_stride, n, r1, i, cfa) : 0.f);
-    __syncthreads();
-    const float2 *r = fft::run<-1, true>(a, b, pl);
-    float2 *d0 = dst + ((long long)blockIdx.y * n + r0) * nh;
-    float2 *d1 = d0 + nh;
-    for (int k = threadIdx.x; k < nh; k += blockDim.x) {
-        const float2 z = r[k], zc = r[k == 0 ? 0 : n - k];
-        d0[k] = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y));     // X[k]
-        if (has1) d1[k] = make_float2(0.5f * (z.y + zc.y), 0.5f * (zc.x - z.x));   // Y[k]
-    }
-}
 
 // XCD-aware order of the row-pair workgroups of the transposed-layout kernels
 // below: the dispatcher deals consecutive workgroups round-robin over the 8
@@ -220,10 +165,13 @@ __device__ __forceinline__ void pair_frame(int &pair, int &frame) {
     frame = (int)(w / np);
 }
 
-// k_rows_real2_fwd writing the half spectra straight into the column-major
-// layout the column pass reads ([nh][n] per frame: column k's n values
-// contiguous), replacing the rectangular transpose kernel: rows r0, r0 + 1
-// of column k are adjacent, so each k is one 16-byte store.
+// rows 2j, 2j + 1 of a frame -> their half spectra, written straight into the
+// column-major layout the column pass reads ([nh][n] per frame: column k's n
+// values contiguous): rows r0, r0 + 1 of column k are adjacent, so each k is
+// one 16-byte store.  (Row-major spectra and a rectangular transpose kernel
+// between the passes lost: 29.0 ms against 27.6 ms, profiles/README.md r05x.)
+// T: float selections, or WORD ones (DATA_USHORT sequences: (float)data,
+// after interpolate_nongreen_ushort for CFA frames)
 template <class T>
 __global__ __launch_bounds__(fft::kThreads) void k_rows_real2_fwd_t(Plan pl, const T *src, long long row_stride,
                                                                     long long frame_stride, float2 *dst,
@@ -259,8 +207,11 @@ template __global__ void k_rows_real2_fwd_t<float>(Plan, const float *, long lon
 template __global__ void k_rows_real2_fwd_t<uint16_t>(Plan, const uint16_t *, long long, long long, float2 *,
                                                       fft::Cfa);
 
-// k_rows_c2r2_argmax reading the column-major half spectra directly (X[q],
-// Y[q] of rows r0, r0 + 1: one 16-byte load per q)
+// inverse row pass on the half spectra of rows 2j, 2j + 1, read from the
+// column-major layout directly (X[q], Y[q] of rows r0, r0 + 1: one 16-byte
+// load per q), + first-max argmax of both real rows.  best[frame] =
+// (ord(value) << 32) | ~index: atomicMax keeps the largest value and, among
+// equal values, the smallest row-major index.
 __global__ __launch_bounds__(fft::kThreads) void k_rows_c2r2_argmax_t(Plan pl, const float2 *data,
                                                                       unsigned long long *best) {
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
@@ -313,52 +264,8 @@ __global__ __launch_bounds__(fft::kThreads) void k_rows_c2r2_argmax_t(Plan pl, c
     }
 }
 
-// inverse row pass on half spectra rows 2j, 2j+1 (pitch nh) + argmax of both
-// real rows (first strict maximum in row-major order, packed u64 atomicMax:
-// ordered float value, then the complement of the row-major index)
-__global__ __launch_bounds__(fft::kThreads) void k_rows_c2r2_argmax(Plan pl, const float2 *data,
-                                                                    unsigned long long *best) {
-    extern __shared__ __attribute__((aligned(16))) float2 lds[];
-    __shared__ unsigned long long wbest[fft::kThreads / 64];
-    const int n = pl.n, nh = n / 2 + 1;
-    float2 *a = lds, *b = lds + n;
-    const int r0 = 2 * blockIdx.x, r1 = r0 + 1;
-    const bool has1 = r1 < n;
-    const float2 *X = data + ((long long)blockIdx.y * n + r0) * nh;
-    const float2 *Y = X + nh;
-    for (int k = threadIdx.x; k < n; k += blockDim.x) {
-        const bool lo = k < nh;
-        const int q = lo ? k : n - k;
-        float2 x = X[q], y = has1 ? Y[q] : make_float2(0.f, 0.f);
-        if (!lo) { x.y = -x.y; y.y = -y.y; }                    // Hermitian extension
-        a[k] = make_float2(x.x - y.y, x.y + y.x);               // Z = X + i Y
-    }
-    __syncthreads();
-    const float2 *r = fft::run<+1, true>(a, b, pl);
-    unsigned long long m = 0;
-    const uint32_t base0 = (uint32_t)r0 * (uint32_t)n, base1 = (uint32_t)r1 * (uint32_t)n;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const unsigned long long k0 = ((unsigned long long)ord(r[i].x) << 32) | (uint32_t)~(base0 + (uint32_t)i);
-        m = k0 > m ? k0 : m;
-        if (has1) {
-            const unsigned long long k1 = ((unsigned long long)ord(r[i].y) << 32) | (uint32_t)~(base1 + (uint32_t)i);
-            m = k1 > m ? k1 : m;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(m, off, 64);
-        m = o > m ? o : m;
-    }
-    if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); w++) m = wbest[w] > m ? wbest[w] : m;
-        atomicMax(best + blockIdx.y, m);
-    }
-}
-
 // rectangular transpose of `batch` planes: in [rows][cols] -> out [cols][rows]
+// (used by rl_fft.hip)
 __global__ __launch_bounds__(256) void k_transpose_rect(const float2 *in, float2 *out, int rows, int cols) {
     __shared__ float2 tile[32][33];
     const long long off = (long long)blockIdx.z * rows * cols;
@@ -400,10 +307,6 @@ __global__ __launch_bounds__(256) void k_nongreen(float *img, long long stride, 
     // reads only green pixels, writes only non-green ones: safe in place
     img[(long long)row * stride + col] = nongreen(img, stride, w, h, row, col, cfa);
 }
-
-template __global__ void k_rows_real2_fwd<float>(Plan, const float *, long long, long long, float2 *, fft::Cfa);
-template __global__ void k_rows_real2_fwd<uint16_t>(Plan, const uint16_t *, long long, long long, float2 *,
-                                                    fft::Cfa);
 
 // interpolate_nongreen_ushort in place on a device image (reads only green
 // pixels, writes only non-green ones)

@@ -11,10 +11,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fft_plan.h"
+
 namespace sgpu {
 namespace fft {
 
-constexpr int kMaxFactors = 24;
 constexpr int kMaxLen = 8192;       // 2 x N x 8 bytes of LDS (128 KiB at N = 8192)
 #ifndef SGPU_FFT_THREADS
 #define SGPU_FFT_THREADS 512

@@ -10,11 +10,12 @@
 //   k_q_subsample_all  s x s block means of all levels from one read of the
 //                  selection (LDS tiles), summed row by row in float as
 //                  SubSample does (:153-164), then / (float)(s*s)
-//   k_q_smooth     the 3x3 box of _smooth_image_float (:222-250): the
+//   k_q_smooth_gradient, per level:
+//     smooth       the 3x3 box of _smooth_image_float (:222-250): the
 //                  reference smooths in place from line buffers, i.e. every
 //                  output reads the unsmoothed neighbours; same summation
 //                  order, edges copied
-//   k_q_gradient   Gradient (:166-219): pixels >= THRESHOLD_FLOAT inside the
+//     gradient     Gradient (:166-219): pixels >= THRESHOLD_FLOAT inside the
 //                  10% margin flag their 3x3 neighbourhood; the flagged
 //                  pixels of the margin region sum d1^2 + d2^2 in f64 (d1, d2
 //                  float differences).  Per-block f64 partials in a fixed
@@ -25,7 +26,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <vector>
 
 #include "sgpu_internal.h"
@@ -38,49 +38,12 @@ constexpr double QMARGIN = 0.1;                // quality.h:25
 constexpr int QSUBSAMPLE_MIN = 3, QSUBSAMPLE_MAX = 5, QSUBSAMPLE_INC = 1;
 constexpr int QT = 256;
 
-__global__ __launch_bounds__(QT) void k_q_subsample(const float *frames, long long row_stride, long long frame_stride,
-                                                    int s, int xs, int ys, float *buf) {
-    const int f = blockIdx.z;
-    const long long i = (long long)blockIdx.x * QT + threadIdx.x;
-    if (i >= (long long)xs * ys) return;
-    const int x = (int)(i % xs), y = (int)(i / xs);
-    const float *p = frames + (long long)f * frame_stride + (long long)(y * s) * row_stride + (long long)x * s;
-    float v = 0.f;
-    for (int r = 0; r < s; ++r) {
-        for (int c = 0; c < s; ++c) v += p[c];
-        p += row_stride;
-    }
-    buf[(long long)f * xs * ys + i] = v / (float)(s * s);
-}
-
-__global__ __launch_bounds__(QT) void k_q_smooth(const float *in, int xs, int ys, float *out) {
-    const int f = blockIdx.z;
-    const long long i = (long long)blockIdx.x * QT + threadIdx.x;
-    if (i >= (long long)xs * ys) return;
-    int x, y;
-    if (i < 0x7fffffffLL) {       // 32-bit division when the index fits
-        x = (int)((unsigned)i % (unsigned)xs);
-        y = (int)((unsigned)i / (unsigned)xs);
-    } else {
-        x = (int)(i % xs);
-        y = (int)(i / xs);
-    }
-    const float *b = in + (long long)f * xs * ys;
-    float r = b[i];
-    if (y >= 1 && y < ys - 1 && x >= 1 && x < xs - 1) {
-        const float *p = b + (long long)(y - 1) * xs, *c = p + xs, *n = c + xs;
-        const float v = (p[x - 1] + p[x]) + (p[x + 1] + c[x - 1]) + (c[x] + c[x + 1]) + (n[x - 1] + n[x]) + n[x + 1];
-        r = v * (1.f / 9.f);
-    }
-    out[(long long)f * xs * ys + i] = r;
-}
-
-
-// Single-read subsample (default; SGPU_QE_FUSED=0 selects k_q_subsample per
-// level): every active level's s x s blocks from one LDS tile of TR x TC
-// pixels (multiples of 3, 4 and 5, so no block straddles tiles); the sums
-// run over LDS in SubSample's order.  60 x 120 tiles (29 KB) keep 5 blocks
-// per CU; 60 x 240 tiles were slower (2 blocks per CU).
+// Single-read subsample: every active level's s x s blocks from one LDS tile
+// of TR x TC pixels (multiples of 3, 4 and 5, so no block straddles tiles);
+// the sums run over LDS in SubSample's order (one kernel per level, each
+// reading the selection from HBM again, was the form it replaced).  60 x 120
+// tiles (29 KB) keep 5 blocks per CU; 60 x 240 tiles were slower (2 blocks
+// per CU).  VEC: 16-byte loads, for selections the host finds aligned.
 constexpr int TR = 60, TC = 120;
 struct Levels {
     int n;
@@ -149,65 +112,11 @@ struct QPart {
     unsigned long long flagged, above;
 };
 
-__global__ __launch_bounds__(QT) void k_q_gradient(const float *sm, int xs, int ys, int xb, int yb, QPart *part) {
-    const int f = blockIdx.z;
-    const float *b = sm + (long long)f * xs * ys;
-    const int rw = xs - 2 * xb, rh = ys - 2 * yb;
-    const long long nreg = (rw > 0 && rh > 0) ? (long long)rw * rh : 0;
-    double sum = 0.0;
-    unsigned long long flagged = 0, above = 0;
-    // the grid-stride walk in row-major region order, with (x, y) advanced by
-    // the stride's quotient / remainder instead of a 64-bit division per pixel
-    const long long step = (long long)gridDim.x * QT;
-    long long i = (long long)blockIdx.x * QT + threadIdx.x;
-    int cx = rw > 0 ? (int)(i % rw) : 0, cy = rw > 0 ? (int)(i / rw) : 0;
-    const int sx = rw > 0 ? (int)(step % rw) : 0, sy = rw > 0 ? (int)(step / rw) : 0;
-    for (; i < nreg; i += step, cx += sx, cy += sy) {
-        if (cx >= rw) {
-            cx -= rw;
-            ++cy;
-        }
-        const int x = xb + cx, y = yb + cy;
-        const long long o = (long long)y * xs + x;
-        if (b[o] >= THRESHOLD_FLOAT) ++above;
-        bool map = false;
-        for (int dy = -1; dy <= 1 && !map; ++dy) {
-            const int yy = y + dy;
-            if (yy < yb || yy >= ys - yb) continue;
-            for (int dx = -1; dx <= 1; ++dx) {
-                const int xx = x + dx;
-                if (xx >= xb && xx < xs - xb && b[(long long)yy * xs + xx] >= THRESHOLD_FLOAT) { map = true; break; }
-            }
-        }
-        if (map) {
-            const double d1 = (double)(b[o] - b[o + 1]);
-            const double d2 = (double)(b[o] - b[o + xs]);
-            sum += (d1 * d1 + d2 * d2);
-            ++flagged;
-        }
-    }
-    __shared__ double ss[QT];
-    __shared__ unsigned long long sf[QT], sa[QT];
-    ss[threadIdx.x] = sum;
-    sf[threadIdx.x] = flagged;
-    sa[threadIdx.x] = above;
-    __syncthreads();
-    for (int d = QT / 2; d > 0; d >>= 1) {
-        if (threadIdx.x < (unsigned)d) {
-            ss[threadIdx.x] += ss[threadIdx.x + d];
-            sf[threadIdx.x] += sf[threadIdx.x + d];
-            sa[threadIdx.x] += sa[threadIdx.x + d];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[(size_t)f * gridDim.x + blockIdx.x] = QPart{ss[0], sf[0], sa[0]};
-}
-
-// Smooth + gradient in one pass (default; SGPU_QE_SPLIT=1 selects the two
-// kernels above): a 64 x 16 tile of the margin region per block, the raw
-// subsampled values with a 2-pixel halo in LDS, the 3x3 box of k_q_smooth
-// (same expression, same edge rule) for the tile with a 1-pixel halo, then
-// k_q_gradient's flags and sums.  One partial per tile.
+// Smooth + gradient in one pass (a smoothed plane in HBM between two kernels
+// was the form it replaced): a 64 x 16 tile of the margin region per block,
+// the raw subsampled values with a 2-pixel halo in LDS, the 3x3 box of the
+// smoothing for the tile with a 1-pixel halo, then the gradient's flags and
+// sums.  One partial per tile.
 constexpr int GX = 64, GY = 16;
 __global__ __launch_bounds__(QT) void k_q_smooth_gradient(const float *in, int xs, int ys, int xb, int yb,
                                                           QPart *part) {
@@ -441,9 +350,6 @@ extern "C" int sgpu_quality_estimate_device(sgpu_context *c, const float *d_fram
         } while (width / subsample == xs && height / subsample == ys);
     }
     std::vector<double> dval((size_t)nframes, 0.0);
-    const int nblk_g = 64;
-    const char *qs = std::getenv("SGPU_QE_SPLIT");     // "1": separate smooth + gradient kernels (A/B knob)
-    const bool split = qs && qs[0] == '1';
     if (L.n > 0) {
         size_t off[3], tot = 0, poff[4] = {0, 0, 0, 0};
         unsigned gx[3], gy[3];
@@ -452,51 +358,29 @@ extern "C" int sgpu_quality_estimate_device(sgpu_context *c, const float *d_fram
             tot += (size_t)L.xs[l] * L.ys[l] * nframes;
             const int yb = (int)((double)L.ys[l] * QMARGIN) + 1, xb = (int)((double)L.xs[l] * QMARGIN) + 1;
             const int rw = L.xs[l] - 2 * xb, rh = L.ys[l] - 2 * yb;
-            gx[l] = split ? nblk_g : (unsigned)std::max(1, (rw + GX - 1) / GX);
-            gy[l] = split ? 1 : (unsigned)std::max(1, (rh + GY - 1) / GY);
+            gx[l] = (unsigned)std::max(1, (rw + GX - 1) / GX);
+            gy[l] = (unsigned)std::max(1, (rh + GY - 1) / GY);
             poff[l + 1] = poff[l] + (size_t)gx[l] * gy[l] * nframes;
         }
-        const size_t big = (size_t)L.xs[0] * L.ys[0] * nframes;
         int rc;
-        if ((rc = c->qe_buf.ensure((tot + big) * sizeof(float))) ||
-            (rc = c->qe_part.ensure(sizeof(QPart) * poff[L.n])))
+        if ((rc = c->qe_buf.ensure(tot * sizeof(float))) || (rc = c->qe_part.ensure(sizeof(QPart) * poff[L.n])))
             return rc;
-        float *base = (float *)c->qe_buf.p, *sm = base + tot;
+        float *base = (float *)c->qe_buf.p;
         for (int l = 0; l < L.n; ++l) L.buf[l] = base + off[l];
-        const char *fz = std::getenv("SGPU_QE_FUSED");   // "0": one pass per level (A/B knob)
-        if (!(fz && fz[0] == '0')) {
-            const dim3 tg((unsigned)((width + TC - 1) / TC), (unsigned)((height + TR - 1) / TR), (unsigned)nframes);
-            const char *qv = std::getenv("SGPU_QE_VEC");     // "0": scalar loads (A/B knob)
-            const bool vec = !(qv && qv[0] == '0') && ((uintptr_t)d_frames % 16 == 0) && row_stride % 4 == 0 &&
-                             (nframes == 1 || frame_stride % 4 == 0) && width % 4 == 0;
-            if (vec)
-                hipLaunchKernelGGL(k_q_subsample_all<true>, tg, dim3(QT), 0, c->stream, d_frames,
-                                   (long long)row_stride, (long long)frame_stride, width, height, L);
-            else
-                hipLaunchKernelGGL(k_q_subsample_all<false>, tg, dim3(QT), 0, c->stream, d_frames,
-                                   (long long)row_stride, (long long)frame_stride, width, height, L);
-        } else {
-            for (int l = 0; l < L.n; ++l) {
-                const long long n = (long long)L.xs[l] * L.ys[l];
-                const dim3 g((unsigned)((n + QT - 1) / QT), 1, (unsigned)nframes);
-                hipLaunchKernelGGL(k_q_subsample, g, dim3(QT), 0, c->stream, d_frames, (long long)row_stride,
-                                   (long long)frame_stride, L.s[l], L.xs[l], L.ys[l], L.buf[l]);
-            }
-        }
+        const dim3 tg((unsigned)((width + TC - 1) / TC), (unsigned)((height + TR - 1) / TR), (unsigned)nframes);
+        const bool vec = ((uintptr_t)d_frames % 16 == 0) && row_stride % 4 == 0 &&
+                         (nframes == 1 || frame_stride % 4 == 0) && width % 4 == 0;
+        if (vec)
+            hipLaunchKernelGGL(k_q_subsample_all<true>, tg, dim3(QT), 0, c->stream, d_frames, (long long)row_stride,
+                               (long long)frame_stride, width, height, L);
+        else
+            hipLaunchKernelGGL(k_q_subsample_all<false>, tg, dim3(QT), 0, c->stream, d_frames, (long long)row_stride,
+                               (long long)frame_stride, width, height, L);
         for (int l = 0; l < L.n; ++l) {
             const int xs = L.xs[l], ys = L.ys[l];
             const int yb = (int)((double)ys * QMARGIN) + 1, xb = (int)((double)xs * QMARGIN) + 1;
-            QPart *pl = (QPart *)c->qe_part.p + poff[l];
-            if (split) {
-                const long long n = (long long)xs * ys;
-                const dim3 g((unsigned)((n + QT - 1) / QT), 1, (unsigned)nframes);
-                hipLaunchKernelGGL(k_q_smooth, g, dim3(QT), 0, c->stream, L.buf[l], xs, ys, sm);
-                hipLaunchKernelGGL(k_q_gradient, dim3(nblk_g, 1, nframes), dim3(QT), 0, c->stream, sm, xs, ys, xb,
-                                   yb, pl);
-            } else {
-                hipLaunchKernelGGL(k_q_smooth_gradient, dim3(gx[l], gy[l], nframes), dim3(QT), 0, c->stream,
-                                   L.buf[l], xs, ys, xb, yb, pl);
-            }
+            hipLaunchKernelGGL(k_q_smooth_gradient, dim3(gx[l], gy[l], nframes), dim3(QT), 0, c->stream, L.buf[l], xs,
+                               ys, xb, yb, (QPart *)c->qe_part.p + poff[l]);
         }
         HIP_TRY(hipGetLastError());
         std::vector<QPart> hp(poff[L.n]);

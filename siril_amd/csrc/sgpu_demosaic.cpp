@@ -19,19 +19,14 @@ struct Img {
     int W, H;
     unsigned char cf[4];
     const unsigned *mm;
-    int remap;
 };
 __global__ void k_minmax(const float *buf, long long n, unsigned *mm);
 __global__ void k_superpixel(const float *buf, int W, int H, int pattern, float *out);
 __global__ void k_bilinear_siril(const uint16_t *bay, int W, int H, int tile, int byte, uint16_t *rgb);
 template <class T, class O>
-int launch_rcd(Img g, const T *buf, O *rgb, int byte, int variant, hipStream_t s);
-template <class T, class O>
 int launch_rcd_multipass(Img g, const T *buf, O *rgb, int byte, float *ws, hipStream_t s);
-template <int TX, int TY, class T, class O>
-int launch_rcd_split(Img g, const T *buf, O *rgb, int byte, float *ws, hipStream_t s);
 template <class T, class O>
-int launch_bayerfast(Img g, const T *buf, O *rgb, int byte, float *ws, hipStream_t s);
+int launch_bayerfast(Img g, const T *buf, O *rgb, int byte, hipStream_t s);
 }  // namespace dm
 }  // namespace sgpu
 
@@ -42,7 +37,19 @@ enum { BAYER_BILINEAR = 0, BAYER_RCD = 8, XTRANS = 9 };
 enum { BAYER_FILTER_RGGB = 0, BAYER_FILTER_GRBG = 3 };
 
 // pattern_to_cfarray (algos/demosaicing_rtp.cpp:20-41)
-const unsigned char kCfarray[4][4] = {{0, 1, 1, 2}, {2, 1, 1, 0}, {1, 2, 0, 1}, {1, 0, 2, 1}};
+constexpr unsigned char kCfarray[4][4] = {{0, 1, 1, 2}, {2, 1, 1, 0}, {1, 2, 0, 1}, {1, 0, 2, 1}};
+
+// green on a checkerboard: the premise of the bayerfast pair kernel
+// (k_bf_pairs), which is the only bayerfast kernel
+constexpr bool bayer_checkerboard(const unsigned char (&cf)[4]) {
+    return (cf[0] == 1) == (cf[3] == 1) && (cf[1] == 1) == (cf[2] == 1) && (cf[0] == 1) != (cf[1] == 1);
+}
+static_assert(bayer_checkerboard(kCfarray[0]) && bayer_checkerboard(kCfarray[1]) &&
+                  bayer_checkerboard(kCfarray[2]) && bayer_checkerboard(kCfarray[3]),
+              "every pattern check_rcd_args admits must have its green sites on a checkerboard");
+
+// workspace planes of launch_rcd_multipass
+constexpr size_t kRcdPlanes = 7;
 
 // the librtprocess switch (demosaicing_rtp.cpp:141-160, 312-330): BAYER_BILINEAR
 // -> bayerfast_demosaic, BAYER_RCD and unknown values (`default: case
@@ -68,33 +75,6 @@ float ord2f(unsigned o) {
 
 }  // namespace
 
-namespace {
-// SGPU_RCD_FUSED: unset / "0" the step-per-kernel pipeline (default: 1.10 ms
-// per 6000x4000 frame with seven passes, 0.90 ms with steps 1.1-2 and 4.1 in
-// one pass, k_dir_pq), "3" the two-kernel split (steps
-// 1-4.1 and 4.2-4.3 with LDS halos, 2.75x the traffic floor instead of ~16x,
-// but 1.32 ms: round 4), "1" one LDS-tiled kernel (64 x 32 tiles, 1.26 ms),
-// "2" the same with 32 x 32 tiles; all are bitwise identical
-int rcd_mode() {
-    const char *e = std::getenv("SGPU_RCD_FUSED");
-    if (!e || !*e) return 0;
-    return std::atoi(e);
-}
-template <class T, class O>
-int run_rcd(int mode, sgpu::dm::Img g, const T *buf, O *rgb, int byte, float *ws, hipStream_t s) {
-    if (mode == 1 || mode == 2) return sgpu::dm::launch_rcd(g, buf, rgb, byte, mode == 2 ? 1 : 0, s);
-    if (mode == 0) return sgpu::dm::launch_rcd_multipass(g, buf, rgb, byte, ws, s);
-    return sgpu::dm::launch_rcd_split<64, 32>(g, buf, rgb, byte, ws, s);
-}
-}  // namespace
-
-// XCD-contiguous tile order of the stencil kernels (demosaic.hip DM_XY);
-// SGPU_DM_REMAP=0: the dispatcher's order (A/B)
-static int dm_remap() {
-    static const int r = !std::getenv("SGPU_DM_REMAP") || std::atoi(std::getenv("SGPU_DM_REMAP")) != 0;
-    return r;
-}
-
 extern "C" int sgpu_debayer_device(sgpu_context *c, const float *d_buf, int width, int height, int interpolation,
                                    int pattern, float *d_rgb) {
     if (!c || !d_buf || !d_rgb) return fail(SGPU_BAD_ARGUMENT, "null argument");
@@ -103,10 +83,7 @@ extern "C" int sgpu_debayer_device(sgpu_context *c, const float *d_buf, int widt
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const long long n = (long long)width * height;
-    const int mode = rcd_mode();
-    if (((mode != 1 && mode != 2) || is_bilinear(interpolation)) &&
-        (r = c->dm_ws.ensure((size_t)n * 8 * sizeof(float))))
-        return r;
+    if ((r = c->dm_ws.ensure((size_t)n * kRcdPlanes * sizeof(float)))) return r;
     if ((r = c->dm_mm.ensure(64))) return r;
     float *ws = (float *)c->dm_ws.p;
     unsigned *mm = (unsigned *)c->dm_mm.p;
@@ -128,9 +105,8 @@ extern "C" int sgpu_debayer_device(sgpu_context *c, const float *d_buf, int widt
     g.H = height;
     std::memcpy(g.cf, kCfarray[pattern], 4);
     g.mm = mm;
-    g.remap = dm_remap();
-    r = is_bilinear(interpolation) ? sgpu::dm::launch_bayerfast(g, d_buf, d_rgb, 0, ws, s)
-                                   : run_rcd(mode, g, d_buf, d_rgb, 0, ws, s);
+    r = is_bilinear(interpolation) ? sgpu::dm::launch_bayerfast(g, d_buf, d_rgb, 0, s)
+                                   : sgpu::dm::launch_rcd_multipass(g, d_buf, d_rgb, 0, ws, s);
     if (r) return fail(SGPU_NO_DEVICE, "debayer launch failed");
     unsigned h_mm[2];
     HIP_TRY(hipMemcpyAsync(h_mm, mm, sizeof h_mm, hipMemcpyDeviceToHost, s));
@@ -151,10 +127,7 @@ extern "C" int sgpu_debayer_u16_device(sgpu_context *c, const uint16_t *d_buf, i
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const long long n = (long long)width * height;
-    const int mode = rcd_mode();
-    if (((mode != 1 && mode != 2) || is_bilinear(interpolation)) &&
-        (r = c->dm_ws.ensure((size_t)n * 8 * sizeof(float))))
-        return r;
+    if ((r = c->dm_ws.ensure((size_t)n * kRcdPlanes * sizeof(float)))) return r;
     if ((r = c->dm_mm.ensure(64))) return r;
     // no normalisation in the 16-bit wrapper: min / max pinned to 0 / 65535
     // make the kernels' (x - min) * factor and v * invfactor + min exact
@@ -169,10 +142,10 @@ extern "C" int sgpu_debayer_u16_device(sgpu_context *c, const uint16_t *d_buf, i
     g.H = height;
     std::memcpy(g.cf, kCfarray[pattern], 4);
     g.mm = mm;
-    g.remap = dm_remap();
     const int byte = bit_depth == 8;         // BYTE_IMG: roundf_to_BYTE (demosaicing_rtp.cpp:206-210)
-    r = is_bilinear(interpolation) ? sgpu::dm::launch_bayerfast(g, d_buf, d_rgb, byte, (float *)c->dm_ws.p, s)
-                                   : run_rcd(mode, g, d_buf, d_rgb, byte, (float *)c->dm_ws.p, s);
+    r = is_bilinear(interpolation)
+            ? sgpu::dm::launch_bayerfast(g, d_buf, d_rgb, byte, s)
+            : sgpu::dm::launch_rcd_multipass(g, d_buf, d_rgb, byte, (float *)c->dm_ws.p, s);
     if (r) return fail(SGPU_NO_DEVICE, "debayer launch failed");
     sgpu_host::mark(c);
     sgpu_host::mark(c);

@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -18,15 +17,7 @@ namespace sgpu {
 namespace dft {
 __global__ void k_nongreen(float *img, long long stride, int w, int h, sgpu::fft::Cfa cfa);
 __global__ void k_rows_fwd(Plan pl, float2 *data, long long plane);
-__global__ void k_rows_xpow_bwd(Plan pl, const float2 *fref, float2 *data, long long plane);
-__global__ void k_cols_fwd_xpow_bwd(Plan pl, const float2 *fref, float2 *data, long long plane, int remap);
-template <class T>
-__global__ void k_rows_real2_fwd(Plan pl, const T *src, long long row_stride, long long frame_stride,
-                                 float2 *dst, sgpu::fft::Cfa cfa);
-extern template __global__ void k_rows_real2_fwd<float>(Plan, const float *, long long, long long, float2 *,
-                                                        sgpu::fft::Cfa);
-extern template __global__ void k_rows_real2_fwd<uint16_t>(Plan, const uint16_t *, long long, long long, float2 *,
-                                                           sgpu::fft::Cfa);
+__global__ void k_cols_fwd_xpow_bwd(Plan pl, const float2 *fref, float2 *data, long long plane);
 __global__ void k_nongreen16(uint16_t *img, long long stride, int w, int h, sgpu::fft::Cfa cfa);
 template <class T>
 __global__ void k_nongreen_pass(const T *orig, long long so, const T *prev, T *out, int w, int h, sgpu::fft::Cfa cfa);
@@ -34,7 +25,6 @@ extern template __global__ void k_nongreen_pass<float>(const float *, long long,
                                                        sgpu::fft::Cfa);
 extern template __global__ void k_nongreen_pass<uint16_t>(const uint16_t *, long long, const uint16_t *, uint16_t *,
                                                           int, int, sgpu::fft::Cfa);
-__global__ void k_rows_c2r2_argmax(Plan pl, const float2 *data, unsigned long long *best);
 __global__ void k_rows_c2r2_argmax_t(Plan pl, const float2 *data, unsigned long long *best);
 template <class T>
 __global__ void k_rows_real2_fwd_t(Plan pl, const T *src, long long row_stride, long long frame_stride, float2 *dst,
@@ -43,76 +33,16 @@ extern template __global__ void k_rows_real2_fwd_t<float>(Plan, const float *, l
                                                           sgpu::fft::Cfa);
 extern template __global__ void k_rows_real2_fwd_t<uint16_t>(Plan, const uint16_t *, long long, long long, float2 *,
                                                              sgpu::fft::Cfa);
-__global__ void k_transpose_rect(const float2 *in, float2 *out, int rows, int cols);
 __global__ void k_finalize(const unsigned long long *best, int nframes, int n, int *shifts, float *peak);
 }  // namespace dft
 }  // namespace sgpu
 
 namespace {
 
-// radix-10 passes (fft_lds.h bfly10); SGPU_DFT_R10=0 keeps the 8 / 5 / 4 plans (A/B)
-bool r10_enabled() {
-    static const bool on = !(std::getenv("SGPU_DFT_R10") && std::atoi(std::getenv("SGPU_DFT_R10")) == 0);
-    return on;
-}
-
-// radices in pass order: 8s, 10s, 5s, then 4, 3, 2, then any other prime
-bool factorize(int n, Plan &pl) {
-    pl.n = n;
-    pl.nf = 0;
-    auto push = [&](int r) {
-        if (pl.nf >= sgpu::fft::kMaxFactors) return false;
-        pl.radix[pl.nf++] = r;
-        return true;
-    };
-    // SGPU_DFT_PLAN="10,10,8,5": an explicit pass order (A/B of the plan
-    // shape; used when its radices multiply to n and all have butterflies)
-    if (const char *e = std::getenv("SGPU_DFT_PLAN")) {
-        int prod = 1;
-        for (const char *q = e; *q;) {
-            const int r = std::atoi(q);
-            if (r != 2 && r != 3 && r != 4 && r != 5 && r != 8 && r != 10) { prod = 0; break; }
-            if (!push(r)) return false;
-            prod *= r;
-            while (*q && *q != ',') q++;
-            if (*q == ',') q++;
-        }
-        if (prod == n) return true;
-        pl.nf = 0;
-    }
-    int m = n;
-    while (m % 8 == 0) { if (!push(8)) return false; m /= 8; }
-    if (r10_enabled())
-        while (m % 10 == 0) { if (!push(10)) return false; m /= 10; }
-    while (m % 5 == 0) { if (!push(5)) return false; m /= 5; }
-    while (m % 4 == 0) { if (!push(4)) return false; m /= 4; }
-    while (m % 3 == 0) { if (!push(3)) return false; m /= 3; }
-    while (m % 2 == 0) { if (!push(2)) return false; m /= 2; }
-    for (int p = 7; m > 1 && p <= m; p += 2)
-        while (m % p == 0) {
-            if (p > 61) return false;          // large primes: not supported by the LDS kernel
-            if (!push(p)) return false;
-            m /= p;
-        }
-    if (m != 1) return false;
-    // an odd radix first: the first pass writes its outputs R words apart
-    // (Ns = 1), and an even R (8, 10) puts lanes 4-16 ways onto the same LDS
-    // banks; 5 x 10 x 10 x 8 runs the 4000-point rows 5.7 % faster than
-    // 8 x 10 x 10 x 5; every odd-first order measured alike (profiles/r05al_*,
-    // r05am_*)
-    for (int p = 0; p < pl.nf; p++)
-        if (pl.radix[p] & 1) {
-            const int r = pl.radix[p];
-            for (int q = p; q > 0; q--) pl.radix[q] = pl.radix[q - 1];
-            pl.radix[0] = r;
-            break;
-        }
-    return true;
-}
-
 int ensure_plan(sgpu_context *c, int n, Plan &pl) {
     if (n < 2 || n > sgpu::fft::kMaxLen) return fail(SGPU_BAD_ARGUMENT, "DFT size must be in [2, 8192]");
-    if (!factorize(n, pl)) return fail(SGPU_BAD_ARGUMENT, "DFT size has a prime factor > 61");
+    pl.n = n;
+    if (!sgpu::fft::factorize(n, pl.radix, pl.nf)) return fail(SGPU_BAD_ARGUMENT, "DFT size has a prime factor > 61");
     int r;
     if ((r = c->dft_tw.ensure((size_t)n * sizeof(float2)))) return r;
     if (c->dft_n != n) {
@@ -124,13 +54,10 @@ int ensure_plan(sgpu_context *c, int n, Plan &pl) {
         HIP_TRY(hipMemcpy(c->dft_tw.p, tw.data(), n * sizeof(float2), hipMemcpyHostToDevice));
         c->dft_n = n;
         const int lds = 2 * n * (int)sizeof(float2);
-        for (const void *f : {(const void *)sgpu::dft::k_rows_fwd, (const void *)sgpu::dft::k_rows_xpow_bwd,
-                              (const void *)sgpu::dft::k_rows_real2_fwd<float>,
+        for (const void *f : {(const void *)sgpu::dft::k_rows_fwd,
                               (const void *)sgpu::dft::k_rows_real2_fwd_t<float>,
                               (const void *)sgpu::dft::k_rows_real2_fwd_t<uint16_t>,
                               (const void *)sgpu::dft::k_rows_c2r2_argmax_t,
-                              (const void *)sgpu::dft::k_rows_real2_fwd<uint16_t>,
-                              (const void *)sgpu::dft::k_rows_c2r2_argmax,
                               (const void *)sgpu::dft::k_cols_fwd_xpow_bwd})
             HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
@@ -138,37 +65,14 @@ int ensure_plan(sgpu_context *c, int n, Plan &pl) {
     return SGPU_OK;
 }
 
-// The half spectra go to the column pass in the column-major layout: written
-// there directly by the row kernel (default; 16-byte stores per row pair and
-// column, XCD-grouped row pairs) or through the rectangular transpose kernel
-// (SGPU_DFT_TRANSPOSE=1, A/B)
-inline bool dft_transpose_kernel() {
-    static const bool t = std::getenv("SGPU_DFT_TRANSPOSE") && std::atoi(std::getenv("SGPU_DFT_TRANSPOSE")) != 0;
-    return t;
-}
-
-// forward 2-D half spectrum (kx in [0, n/2]), stored transposed as nh rows
-// of n: real row pairs -> (transposed store) -> column FFTs (cols = 0: the
-// column transforms are left to the caller's fused column pass)
+// forward row pass of `batch` selections: real row pairs -> half spectra (kx
+// in [0, n/2]), stored transposed as nh rows of n, the layout the column
+// passes read; the column transforms are the caller's
 template <class T>
-int spectrum_half_T(sgpu_context *c, const Plan &pl, const T *src, long long row_stride,
-                    long long frame_stride, int batch, float2 *t1, float2 *out, const sgpu::fft::Cfa &cfa,
-                    int cols = 1) {
-    const int n = pl.n, nh = n / 2 + 1;
-    const size_t lds = sgpu::fft::plan_lds_bytes(pl);
-    hipStream_t s = c->stream;
-    if (dft_transpose_kernel()) {
-        hipLaunchKernelGGL(sgpu::dft::k_rows_real2_fwd<T>, dim3((n + 1) / 2, batch), dim3(sgpu::fft::kThreads), lds,
-                           s, pl, src, row_stride, frame_stride, t1, cfa);
-        hipLaunchKernelGGL(sgpu::dft::k_transpose_rect, dim3((nh + 31) / 32, (n + 31) / 32, batch), dim3(256), 0, s,
-                           t1, out, n, nh);
-    } else {
-        hipLaunchKernelGGL(sgpu::dft::k_rows_real2_fwd_t<T>, dim3((n + 1) / 2, batch), dim3(sgpu::fft::kThreads),
-                           lds, s, pl, src, row_stride, frame_stride, out, cfa);
-    }
-    if (cols)
-        hipLaunchKernelGGL(sgpu::dft::k_rows_fwd, dim3(nh, batch), dim3(sgpu::fft::kThreads), lds, s, pl, out,
-                           (long long)nh * n);
+int rows_half_T(sgpu_context *c, const Plan &pl, const T *src, long long row_stride, long long frame_stride,
+                int batch, float2 *out, const sgpu::fft::Cfa &cfa) {
+    hipLaunchKernelGGL(sgpu::dft::k_rows_real2_fwd_t<T>, dim3((pl.n + 1) / 2, batch), dim3(sgpu::fft::kThreads),
+                       sgpu::fft::plan_lds_bytes(pl), c->stream, pl, src, row_stride, frame_stride, out, cfa);
     return hipGetLastError() == hipSuccess ? SGPU_OK : fail(SGPU_NO_DEVICE, "DFT spectrum launch failed");
 }
 
@@ -307,14 +211,14 @@ int dft_register(sgpu_context *c, const T *d_ref, long ref_row_stride, const T *
     if (r) return r;
     const int n = size, nh = n / 2 + 1;
     const size_t plane = (size_t)nh * n * sizeof(float2);   // half spectrum
-    // frames per batch: two complex planes each, within ~4 GiB
+    // frames per batch: ~2 GiB of half spectra
     int batch = (int)std::max<size_t>(1, (4ull << 30) / (2 * plane));
     batch = std::min(batch, nframes);
-    if ((r = c->dft_ref.ensure(plane)) || (r = c->dft_t1.ensure(plane * batch)) ||
-        (r = c->dft_t2.ensure(plane * batch)) || (r = c->dft_best.ensure(nframes * sizeof(unsigned long long))))
+    if ((r = c->dft_ref.ensure(plane)) || (r = c->dft_t2.ensure(plane * batch)) ||
+        (r = c->dft_best.ensure(nframes * sizeof(unsigned long long))))
         return r;
     hipStream_t s = c->stream;
-    float2 *fref = (float2 *)c->dft_ref.p, *t1 = (float2 *)c->dft_t1.p, *t2 = (float2 *)c->dft_t2.p;
+    float2 *fref = (float2 *)c->dft_ref.p, *t2 = (float2 *)c->dft_t2.p;
     unsigned long long *best = (unsigned long long *)c->dft_best.p;
     // timing group [pipeline start, stop, -, -] (sgpu_last_timing ms[0])
     c->ev_used = 0;
@@ -337,13 +241,11 @@ int dft_register(sgpu_context *c, const T *d_ref, long ref_row_stride, const T *
         ref_stride = n;
         cfa_t.dim = 0;
     }
-    // reference spectrum (shift_methods.c:165-178)
-    if ((r = spectrum_half_T(c, pl, ref_src, ref_stride, 0, 1, t1, fref, cfa_t))) return r;
     const size_t lds = sgpu::fft::plan_lds_bytes(pl);
-    const char *fz = std::getenv("SGPU_DFT_FUSED");          // "0": separate column passes (A/B knob)
-    const bool fused = !(fz && fz[0] == '0');
-    const char *rm = std::getenv("SGPU_DFT_REMAP");          // "1": frame-fastest XCD-contiguous order (A/B)
-    const int remap = (rm && rm[0] == '1') ? 1 : 0;
+    // reference spectrum (shift_methods.c:165-178): rows, then columns
+    if ((r = rows_half_T(c, pl, ref_src, ref_stride, 0, 1, fref, cfa_t))) return r;
+    hipLaunchKernelGGL(sgpu::dft::k_rows_fwd, dim3(nh, 1), dim3(sgpu::fft::kThreads), lds, s, pl, fref,
+                       (long long)nh * n);
     for (int f0 = 0; f0 < nframes; f0 += batch) {
         const int nb = std::min(batch, nframes - f0);
         if (passes) {
@@ -351,31 +253,17 @@ int dft_register(sgpu_context *c, const T *d_ref, long ref_row_stride, const T *
             if ((r = nongreen_passes<T>(s, d_frames + (long long)f0 * frame_stride, row_stride, frame_stride, nb, n, n,
                                         cfa, passes, stage, stage + (long long)batch * sel)))
                 return r;
-            r = spectrum_half_T(c, pl, (const T *)stage, n, sel, nb, t1, t2, cfa_t, fused ? 0 : 1);
+            r = rows_half_T(c, pl, (const T *)stage, n, sel, nb, t2, cfa_t);
         } else {
-            r = spectrum_half_T(c, pl, d_frames + (long long)f0 * frame_stride, row_stride, frame_stride, nb, t1, t2,
-                                cfa, fused ? 0 : 1);
+            r = rows_half_T(c, pl, d_frames + (long long)f0 * frame_stride, row_stride, frame_stride, nb, t2, cfa);
         }
         if (r) return r;
-        if (fused) {
-            // forward columns, cross power, inverse columns in one LDS pass
-            hipLaunchKernelGGL(sgpu::dft::k_cols_fwd_xpow_bwd, dim3(nh, nb), dim3(sgpu::fft::kThreads), lds, s, pl,
-                               fref, t2, (long long)nh * n, remap);
-        } else {
-            // cross-power spectrum fused into the first inverse pass (columns)
-            hipLaunchKernelGGL(sgpu::dft::k_rows_xpow_bwd, dim3(nh, nb), dim3(sgpu::fft::kThreads), lds, s, pl,
-                               fref, t2, (long long)nh * n);
-        }
+        // forward columns, cross power, inverse columns in one LDS pass
+        hipLaunchKernelGGL(sgpu::dft::k_cols_fwd_xpow_bwd, dim3(nh, nb), dim3(sgpu::fft::kThreads), lds, s, pl, fref,
+                           t2, (long long)nh * n);
         // inverse rows (two real rows per complex transform) + argmax
-        if (dft_transpose_kernel()) {
-            hipLaunchKernelGGL(sgpu::dft::k_transpose_rect, dim3((n + 31) / 32, (nh + 31) / 32, nb), dim3(256), 0, s,
-                               t2, t1, nh, n);
-            hipLaunchKernelGGL(sgpu::dft::k_rows_c2r2_argmax, dim3((n + 1) / 2, nb), dim3(sgpu::fft::kThreads), lds,
-                               s, pl, t1, best + f0);
-        } else {
-            hipLaunchKernelGGL(sgpu::dft::k_rows_c2r2_argmax_t, dim3((n + 1) / 2, nb), dim3(sgpu::fft::kThreads), lds,
-                               s, pl, t2, best + f0);
-        }
+        hipLaunchKernelGGL(sgpu::dft::k_rows_c2r2_argmax_t, dim3((n + 1) / 2, nb), dim3(sgpu::fft::kThreads), lds, s,
+                           pl, t2, best + f0);
         if (hipGetLastError() != hipSuccess) return fail(SGPU_NO_DEVICE, "DFT launch failed");
     }
     hipLaunchKernelGGL(sgpu::dft::k_finalize, dim3((nframes + 255) / 256), dim3(256), 0, s, best, nframes, n,

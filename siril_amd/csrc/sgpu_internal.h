@@ -102,7 +102,7 @@ struct sgpu_context {
     std::vector<float> h_crit;
     // DFT registration workspace
     int dft_n = 0;
-    sgpu_host::DevBuf dft_tw, dft_ref, dft_t1, dft_t2, dft_best, dft_shifts, dft_frames;
+    sgpu_host::DevBuf dft_tw, dft_ref, dft_t2, dft_best, dft_shifts, dft_frames;
     // Richardson-Lucy workspace
     sgpu_host::DevBuf rl_u, rl_e, rl_f, rl_r, rl_w, rl_taps, rl_small, rl_io, rl_reg, rl_gxy;
     // Richardson-Lucy FFT convolution: work planes, taps spectra, twiddles
@@ -180,7 +180,7 @@ struct sgpu_context {
     void release_all() {
         for (sgpu_host::DevBuf *b : {&fb_list, &fb_count, &counts, &scratch, &scale, &offset, &mul,
                                      &shiftx, &weights, &crit, &frames, &out, &rej_lo, &rej_hi, &out16, &pl_drizz, &pl_mask,
-                                     &dft_tw, &dft_ref, &dft_t1, &dft_t2, &dft_best, &dft_shifts,
+                                     &dft_tw, &dft_ref, &dft_t2, &dft_best, &dft_shifts,
                                      &dft_frames, &rl_u, &rl_e, &rl_f, &rl_r, &rl_w, &rl_taps, &rl_small,
                                      &rl_io, &rl_reg, &rl_gxy, &rlf_t1, &rlf_t2, &rlf_ka, &rlf_kb, &rlf_kt, &rlf_tw1, &rlf_tw2, &dm_ws, &dm_mm, &dm_io, &ns_state, &ns_hist, &ns_part, &ns_io, &bn_rows, &qe_buf, &qe_part, &qe_io, &onorm, &ov_ws, &ov_tab,
                                      &fb2_list, &fb2_count, &wz_ws, &wz_cnt, &fe_tab, &fe_dt, &cfa_tmp, &cstripe, &warp_ws, &drz_ws, &cal_rows, &cal_k, &cal_cnt, &cal_plan,

@@ -3,8 +3,8 @@
 //
 // Layout: a group of G consecutive lanes owns one output pixel; lane g holds
 // E = NP/G samples of the pixel's N-deep column in VGPRs.  After the gather
-// the column is sorted with a fully unrolled bitonic network (in-lane
-// compare-exchanges, plus __shfl_xor exchanges across the G lanes), so every
+// the column is sorted with a fully unrolled network (sort_column: in-lane
+// compare-exchanges, then merges across the G lanes), so every
 // order statistic the reference asks quickselect for is an indexed read of
 // the sorted column, and every rejection round of SIGMA / WINSORIZED /
 // PERCENTILE removes a prefix and a suffix: the kept set is an index window
@@ -51,21 +51,9 @@
 #ifndef SGPU_NACC
 #define SGPU_NACC 2
 #endif
-#ifndef SGPU_OPAQUE_FINAL
-#define SGPU_OPAQUE_FINAL 1
-#endif
-#ifndef SGPU_RANGE_FIRST
-#define SGPU_RANGE_FIRST 1
-#endif
-#ifndef SGPU_RECLAMP
-#define SGPU_RECLAMP 1
-#endif
 // timing ablations (diagnostic builds only; results are wrong with any set):
 // SGPU_ABL_NOSORT skips the column sort, SGPU_ABL_ITERS=k runs exactly k
 // Winsorized inner iterations per round, SGPU_ABL_NOREJ skips the rejection
-#ifndef SGPU_MEDIAN_SELECT
-#define SGPU_MEDIAN_SELECT 1      // median stack: pruned selection network (0: the full sort; A/B)
-#endif
 #ifndef SGPU_ABL_NOSORT
 #define SGPU_ABL_NOSORT 0
 #endif
@@ -85,18 +73,8 @@
 #endif
 // slot granularity of the wave-uniform pass ends (4; 2 measured 7x slower:
 // the column loops no longer fully unroll)
-#ifndef SGPU_LATE_PIX
-#define SGPU_LATE_PIX 1
-#endif
-#ifndef SGPU_GATHER_STOP
-#define SGPU_GATHER_STOP 1
-#endif
 #ifndef SGPU_STOP_GRAN
 #define SGPU_STOP_GRAN 4
-#endif
-// A/B: the compare form of count_sigma on the device
-#ifndef SGPU_COUNT_CMP
-#define SGPU_COUNT_CMP 0
 #endif
 
 namespace sgpu {
@@ -370,51 +348,6 @@ template <int NP, int G, int RS = NP / G> SG_HD void sort_column(float (&v)[NP /
     }
 }
 
-// Bitonic sort of the NP-element column spread as E = NP/G per lane; element
-// index i = g*E + e.  Ascending.  (Kept as the reference network for the
-// sort_column A/B: SGPU_SORT_BITONIC=1.)
-template <int NP, int G> SG_HD void bitonic_sort(float (&v)[NP / G], int g) {
-    constexpr int E = NP / G;
-    constexpr int LOGNP = __builtin_ctz(NP);
-    // affine loop counters (log2 k, log2 j) so the loops fully unroll and
-    // every slot index is a compile-time constant (no scratch)
-#pragma unroll
-    for (int lk = 1; lk <= LOGNP; lk++) {
-        const int k = 1 << lk;
-#pragma unroll
-        for (int lj = lk - 1; lj >= 0; lj--) {
-            const int j = 1 << lj;
-            if (j >= E) {
-                // partner lives in lane g ^ (j/E), same slot e.  k > j >= E, so
-                // the direction bit (i & k) is a lane bit: uniform per lane.
-                const bool up = ((g * E) & k) == 0;
-                const bool lower = (g & (j / E)) == 0;
-                const bool take_min = (lower == up);
-#pragma unroll
-                for (int e = 0; e < E; e++) {
-                    const float o = gxchg_rt<G>(v[e], j / E);
-                    const float mn = fminf(v[e], o), mx = fmaxf(v[e], o);
-                    v[e] = take_min ? mn : mx;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < E; e++) {
-                    const int l = e ^ j;
-                    if (l > e) {
-                        const float a = v[e], b = v[l];
-                        const float mn = fminf(a, b), mx = fmaxf(a, b);
-                        bool up;
-                        if (k < E) up = (e & k) == 0;            // compile-time
-                        else up = ((g * E) & k) == 0;            // lane bit (k >= E)
-                        v[e] = up ? mn : mx;
-                        v[l] = up ? mx : mn;
-                    }
-                }
-            }
-        }
-    }
-}
-
 template <int NP, int G, int R> SG_HD void sort_merge_lanes(float (&v)[NP / G], int g) {
     constexpr int E = NP / G;
     if constexpr (R < G) {
@@ -448,15 +381,11 @@ template <int NP, int G, int R> SG_HD void sort_merge_lanes(float (&v)[NP / G], 
     }
 }
 
-#ifndef SGPU_SORT_BITONIC
-#define SGPU_SORT_BITONIC 0
-#endif
 // RS: a bound on the slots per lane that can hold samples (slots e >= RS are
 // +Inf padding in every lane: frames e*G + g >= N); the host guarantees
 // ceil(N / G) <= RS (rs_pick)
 template <int NP, int G, int RS = NP / G> SG_HD void sort_col(float (&v)[NP / G], int g) {
-    if constexpr (SGPU_SORT_BITONIC) bitonic_sort<NP, G>(v, g);
-    else sort_column<NP, G, RS>(v, g);
+    sort_column<NP, G, RS>(v, g);
 }
 // real-slot bound of a launch: the smallest compiled bound >= ceil(N / G)
 // (steps of 4 at E = 64, of 8 at E = 128: the variants of
@@ -519,7 +448,7 @@ template <int E> SG_HD float selu(const float (&v)[E], int idx) {
 }
 
 // Slot layout of the sorted column inside a lane group.  Block (IL = false):
-// lane g holds sorted indices [g*E, (g+1)*E) -- what bitonic_sort produces.
+// lane g holds sorted indices [g*E, (g+1)*E) -- what sort_column produces.
 // Interleaved (IL = true): lane g holds indices g, g+G, g+2G, ... so the
 // padding slots (index >= N) are the same trailing slots e >= ceil(N/G) in
 // every lane and the per-iteration passes can stop there (wave-uniform).
@@ -807,12 +736,10 @@ SG_HD float sd_filled(const float (&v)[NP / G], int n, float fill, float L, floa
     if (!sg.exact && !f32_stable(qm, (sum_bound(sg, stot, xlo, xhi, G * elim) + fabs(st) * 0x1p-50) * rn))
         return -2.f;
     const float mean = (float)qm;                              // (float)(sum / N)
-#if SGPU_RECLAMP
     // recompute the clamp in the second pass instead of keeping E clamped
     // values alive across the reduction (register pressure)
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(L), "+v"(U));
-#endif
 #endif
     double q[SGPU_NACC];
 #pragma unroll
@@ -887,7 +814,7 @@ SG_HD double sum_win(const float (&v)[E], int g, int lo, int hi, int elim = E) {
 template <int E, int G, bool SIGNBIT = true>
 SG_HD void count_sigma(const float (&v)[E], float mf, float tl, float th, int &cl, int &ch,
                        int elim) {
-#if defined(__HIP_DEVICE_COMPILE__) && !SGPU_COUNT_CMP
+#if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (SIGNBIT) {
     // Sign-bit form (no compares, no VCC round trips):
     // fl(mf - x) = -fl(x - mf) (round-to-nearest is symmetric), so with
@@ -1473,24 +1400,16 @@ SG_HD PixOut pixel_sorted(float (&v)[NP / G], int g, int kept, const PixCfg &c) 
     }
     // mean of the kept window (median_and_mean.c:1083-1097)
     SG_PMARK(c.pa, 9);
-#if SGPU_OPAQUE_FINAL
     opaque_col<E>(v);
-#endif
     const int n = hi - lo;
     o.nkept = n;
     // (range first: evaluating the two select trees after the sum doubles
     // the register peak and spills)
     double st;
-#if SGPU_RANGE_FIRST
     o.pmin = ostat<E, G, IL>(v, lo);
     o.pmax = ostat<E, G, IL>(v, hi - 1);
     fill_outside<E, G, IL>(v, g, lo, hi, 0.f, elim);   // out-of-window slots add 0
     st = sum_all<E, G>(v, elim);
-#else
-    st = sum_win<E, G, IL>(v, g, lo, hi, elim);
-    o.pmin = ostat<E, G, IL>(v, lo);
-    o.pmax = ostat<E, G, IL>(v, hi - 1);
-#endif
     o.res = st / (double)n;
     // the output is (float)mean (median_and_mean.c:1725-1727): order-independent
     // when the sum is exact or the float is stable under the order error
@@ -1750,7 +1669,7 @@ __device__ __forceinline__ void gather_column(const KParams &p, float (&v)[E], l
     // per lane in the prep kernel -- measured slower: config 2 15.6 vs 12.0
     // ms with the same prep otherwise, profiles/r06g_ab.txt.  The grouped
     // issue of the loads between the exits is worth more than the moves.)
-    constexpr bool GSTOP = SGPU_GATHER_STOP && !(E == 128 && G == 4);
+    constexpr bool GSTOP = !(E == 128 && G == 4);
     const int elg = GSTOP ? (((N + G - 1) / G) + SGPU_STOP_GRAN - 1) & ~(SGPU_STOP_GRAN - 1) : E;
     // (no zero-initialisation of raw: the stop's exits then had to
     // rematerialise the zeros of every slot not yet loaded on the path that
@@ -1882,7 +1801,7 @@ __device__ __forceinline__ void stack_pixel(const KParams &p, long long pix, int
         o.fallback = 1;
     } else {
 #if !SGPU_ABL_NOSORT
-        if constexpr (RT == KMEDIAN && G == 1 && RS < E && SGPU_MEDIAN_SELECT) {
+        if constexpr (RT == KMEDIAN && G == 1 && RS < E) {
             // the median stack reads ranks N/2 - 1 and N/2 only: the network
             // pruned to what N in this real-slot bucket (rs_pick: N in
             // (RS - step, RS]) can read
@@ -1950,7 +1869,7 @@ void k_stack_sorted(KParams p) {
     } else {
         const long long pix = gid / G;
         if (pix < p.npix)
-            stack_pixel<NP, G, RT, XF, U16, (SGPU_LATE_PIX && NP >= 256), RS>(p, pix, g, rl, rh);
+            stack_pixel<NP, G, RT, XF, U16, (NP >= 256), RS>(p, pix, g, rl, rh);
     }
     add_counts(p, rl, rh);
 }

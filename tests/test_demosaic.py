@@ -114,28 +114,17 @@ def test_rcd_full_frame_properties():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["1", "2", "0", "3"])
 @pytest.mark.parametrize("shape", [(131, 517), (96, 128), (33, 70)])
-def test_rcd_tiles_and_multipass_bit_exact(mode, shape):
-    """The fused LDS-tiled kernel (64x32 and 32x32 tiles, tile edges inside
-    the image and at its border), the step-per-kernel pipeline and the
-    two-kernel split (the default) all equal the restatement bitwise
-    (SGPU_RCD_FUSED selects the variant)."""
-    import os
+def test_rcd_tiles_and_multipass_bit_exact(shape):
+    """The RCD pipeline (one launch of 64x4 tiles per group of steps, tile
+    edges inside the image and at its border, widths that are no multiple of
+    the tile) equals the restatement bitwise."""
     from siril_amd import demosaic
-    old = os.environ.get("SGPU_RCD_FUSED")
-    os.environ["SGPU_RCD_FUSED"] = mode
-    try:
-        for pattern in (0, 3):
-            mos = _mosaic(*shape, pattern, seed=7 + pattern)
-            want = D.debayer_buffer_new_float(mos, D.BAYER_RCD, pattern)
-            got = demosaic.debayer_buffer_new_float(mos, demosaic.BAYER_RCD, pattern)
-            assert np.array_equal(got, want), (mode, shape, pattern)
-    finally:
-        if old is None:
-            os.environ.pop("SGPU_RCD_FUSED", None)
-        else:
-            os.environ["SGPU_RCD_FUSED"] = old
+    for pattern in (0, 3):
+        mos = _mosaic(*shape, pattern, seed=7 + pattern)
+        want = D.debayer_buffer_new_float(mos, D.BAYER_RCD, pattern)
+        got = demosaic.debayer_buffer_new_float(mos, demosaic.BAYER_RCD, pattern)
+        assert np.array_equal(got, want), (shape, pattern)
 
 
 # ---- debayer_buffer_new_ushort (demosaicing_rtp.cpp:74-224) -----------------
@@ -173,36 +162,26 @@ def test_rcd_ushort_gpu_bit_exact(pattern, shape):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["1", "2", "0", "3"])
-def test_rcd_ushort_variants_byte_depth_and_device(mode):
-    """Every RCD variant on 16-bit data, the BYTE_IMG rounding (bit_depth 8,
-    8-bit samples) and the device entry point on an int16 tensor; a constant
-    16-bit frame is not an error (the 16-bit wrapper does not normalise)."""
-    import os
+def test_rcd_ushort_variants_byte_depth_and_device():
+    """RCD on 16-bit data, the BYTE_IMG rounding (bit_depth 8, 8-bit samples)
+    and the device entry point on an int16 tensor; a constant 16-bit frame is
+    not an error (the 16-bit wrapper does not normalise)."""
     import torch
     from siril_amd import demosaic
-    old = os.environ.get("SGPU_RCD_FUSED")
-    os.environ["SGPU_RCD_FUSED"] = mode
-    try:
-        mos = _mosaic16(131, 517, 2, seed=3)
-        assert np.array_equal(demosaic.debayer_buffer_new_ushort(mos, demosaic.BAYER_RCD, 2),
-                              D.debayer_buffer_new_ushort(mos, D.BAYER_RCD, 2))
-        m8 = _mosaic16(96, 128, 0, seed=4, top=255.0)
-        assert np.array_equal(demosaic.debayer_buffer_new_ushort(m8, demosaic.BAYER_RCD, 0, bit_depth=8),
-                              D.debayer_buffer_new_ushort(m8, D.BAYER_RCD, 0, bit_depth=8))
-        dev = torch.from_numpy(mos.view(np.int16)).cuda()
-        out = demosaic.debayer(dev, pattern=2)
-        torch.cuda.synchronize()
-        assert out.dtype == torch.int16
-        assert np.array_equal(out.cpu().numpy().view(np.uint16), D.debayer_buffer_new_ushort(mos, D.BAYER_RCD, 2))
-        flat = np.full((16, 16), 1234, np.uint16)
-        got = demosaic.debayer_buffer_new_ushort(flat)
-        assert got is not None and (got == 1234).all()
-    finally:
-        if old is None:
-            os.environ.pop("SGPU_RCD_FUSED", None)
-        else:
-            os.environ["SGPU_RCD_FUSED"] = old
+    mos = _mosaic16(131, 517, 2, seed=3)
+    assert np.array_equal(demosaic.debayer_buffer_new_ushort(mos, demosaic.BAYER_RCD, 2),
+                          D.debayer_buffer_new_ushort(mos, D.BAYER_RCD, 2))
+    m8 = _mosaic16(96, 128, 0, seed=4, top=255.0)
+    assert np.array_equal(demosaic.debayer_buffer_new_ushort(m8, demosaic.BAYER_RCD, 0, bit_depth=8),
+                          D.debayer_buffer_new_ushort(m8, D.BAYER_RCD, 0, bit_depth=8))
+    dev = torch.from_numpy(mos.view(np.int16)).cuda()
+    out = demosaic.debayer(dev, pattern=2)
+    torch.cuda.synchronize()
+    assert out.dtype == torch.int16
+    assert np.array_equal(out.cpu().numpy().view(np.uint16), D.debayer_buffer_new_ushort(mos, D.BAYER_RCD, 2))
+    flat = np.full((16, 16), 1234, np.uint16)
+    got = demosaic.debayer_buffer_new_ushort(flat)
+    assert got is not None and (got == 1234).all()
 
 
 # ---- Siril's own bilinear decoder (demosaicing_siril.c:203-288) ----------

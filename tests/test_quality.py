@@ -120,33 +120,27 @@ def test_gpu_register_cfa_does_not_touch_frames(ctx, n):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("knob,val", [("SGPU_QE_FUSED", "0"), ("SGPU_QE_VEC", "0"), ("SGPU_QE_SPLIT", "1")])
-def test_gpu_quality_unfused_subsample_path(knob, val):
-    """SGPU_QE_FUSED=0 selects the per-level subsample kernels, SGPU_QE_VEC=0
-    the scalar-load fused kernel, SGPU_QE_SPLIT=1 separate smooth and
-    gradient kernels; same results."""
-    import os
-    import subprocess
-    import sys
-    code = ("import numpy as np, torch\n"
-            "from siril_amd import registration as R, synth\n"
-            "from oracle import quality_ref as Q\n"
-            "base = synth.star_field(300, 400, nstars=200, seed=9)\n"
-            "fr = np.stack([np.roll(base, (i, 2 * i), (0, 1)) * (1 - 0.03 * i) + 0.05 for i in range(3)]).astype(np.float32)\n"
-            "d = torch.from_numpy(fr).cuda()\n"
-            "q = R.quality_estimate(d[:, 20:276, 60:316])\n"
-            "for i in range(3):\n"
-            "    e = Q.quality_estimate_float(fr[i, 20:276, 60:316])\n"
-            "    assert abs(q[i] - e) <= 1e-12 * abs(e), (i, q[i], e)\n"
-            "img = (0.05 + 0.9 * synth.star_field(257, 301, nstars=90, seed=4)).astype(np.float32)\n"
-            "q = R.quality_estimate(img[None])\n"
-            "e = Q.quality_estimate_float(img)\n"
-            "assert abs(q[0] - e) <= 1e-12 * abs(e), (q[0], e)\n"
-            "print('ok')\n")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYTHONPATH=root, **{knob: val})
-    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=root, capture_output=True, text=True, timeout=100)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
+def test_gpu_quality_vector_and_scalar_load_paths(ctx):
+    """Both instantiations of the single-read subsample kernel
+    (k_q_subsample_all): the aligned 256-wide window takes the 16-byte loads;
+    the same window started one column later (width a multiple of 4, pointer
+    not 16-byte aligned) and the 257 x 301 frame (width no multiple of 4)
+    take the scalar loads.  Same results, 1e-12 relative."""
+    import torch
+    from siril_amd import registration as R
+    base = synth.star_field(300, 400, nstars=200, seed=9)
+    fr = np.stack([np.roll(base, (i, 2 * i), (0, 1)) * (1 - 0.03 * i) + 0.05 for i in range(3)]).astype(np.float32)
+    d = torch.from_numpy(fr).cuda()
+    assert d.data_ptr() % 16 == 0
+    for x0 in (60, 61):
+        q = R.quality_estimate(d[:, 20:276, x0:x0 + 256], ctx)
+        for i in range(3):
+            e = Q.quality_estimate_float(fr[i, 20:276, x0:x0 + 256])
+            assert abs(q[i] - e) <= 1e-12 * abs(e), (x0, i, q[i], e)
+    img = (0.05 + 0.9 * synth.star_field(257, 301, nstars=90, seed=4)).astype(np.float32)
+    q = R.quality_estimate(img[None], ctx)
+    e = Q.quality_estimate_float(img)
+    assert abs(q[0] - e) <= 1e-12 * abs(e), (q[0], e)
 
 
 def _u16(img):
