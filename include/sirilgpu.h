@@ -900,6 +900,46 @@ int sgpu_stretch_planes_device(sgpu_context *ctx, const void *d_in, int elem_siz
  * launches; waits for the call) and the number of launches. */
 int sgpu_stretch_last_kernel_ms(sgpu_context *ctx, float *ms, int *nlaunches);
 
+/* ---- edge-preserving filters (the `epf` command) --------------------------- */
+
+/* The specification is DESIGN.md 6n (E0-E7), stated once in
+ * siril_amd/csrc/epf_host.h and restated in tests/epf_ref.py; parity with
+ * Siril (which calls OpenCV) is unpinned.  A plane is width x height samples
+ * (elem_size 2: WORD, divided by 65535; 4: float), widened to double; every
+ * plane is filtered on its own.  The window is d x d, d odd in 3 .. 25 (d = 0:
+ * 2*round(1.5*ss) + 1, clamped to 3 .. 25), its taps reflected at the plane's
+ * edges as the wavelets' are.  Mode 1 is the guided filter (He, Sun, Tang) with
+ * eps = si*si (si in [0, 1] sample units), guided by a second set of planes of
+ * the same geometry or, when d_guide is NULL, by the input; box sums are added
+ * in double in a fixed order, a and b are kept as float in the context's
+ * workspace (two float planes per input plane), and ss is read only for d = 0.
+ * Mode 0, the bilateral filter, is specified in 6n but not built: it is
+ * refused.  out = m when modulation is 1, otherwise modulation*m +
+ * (1 - modulation)*x in float.  The host, the device and the restatement give
+ * the same bits.  The call is asynchronous on the context's stream and copies
+ * nothing to the host.  nplanes == 0 does nothing. */
+#define SGPU_EPF_BILATERAL 0     /* refused: not built */
+#define SGPU_EPF_GUIDED 1
+#define SGPU_EPF_MAX_LAUNCHES 2
+/* SGPU_OK, or SGPU_BAD_ARGUMENT: mode other than 1, d even or outside {0} and
+ * 3 .. 25, (d - 1)/2 above min(width, height) - 1, si not finite or <= 0, ss
+ * not finite or <= 0 (d = 0 only), modulation not finite or outside [0, 1], a
+ * side above 65535.  Host only. */
+int sgpu_epf_check(int width, int height, int mode, int d, double si, double ss, float modulation);
+/* Plane p at d_in + p*plane_stride samples, its guide at d_guide +
+ * p*guide_stride samples of guide_elem_size, its result at d_out +
+ * p*out_stride floats.  Also SGPU_BAD_ARGUMENT: elem_size other than 2 or 4, a
+ * stride below width*height, a guide whose element size or stride is bad, an
+ * output range that overlaps the input or the guide. */
+int sgpu_epf_planes_device(sgpu_context *ctx, const void *d_in, int elem_size, int nplanes, int width, int height,
+		long plane_stride, const void *d_guide, int guide_elem_size, long guide_stride, int mode, int d,
+		double si, double ss, float modulation, float *d_out, long out_stride);
+/* Kernel times of the context's last epf call, none after a refused one (HIP
+ * events between its two launches; waits for the call).  what[k] =
+ * 100*kernel + d with kernel 1: a and b, 2: the output.  Arrays of
+ * SGPU_EPF_MAX_LAUNCHES. */
+int sgpu_epf_last_kernel_ms(sgpu_context *ctx, float *ms, int *what, int *nlaunches);
+
 /* ---- star detection and star-based global registration ------------------- */
 
 /* Arithmetic: the specification in DESIGN.md 6f, restated in

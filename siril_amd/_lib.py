@@ -58,6 +58,7 @@ EXPORTS = (
     "sgpu_fmedian_check", "sgpu_fmedian_planes_device", "sgpu_fmedian_last_kernel_ms",
     "sgpu_stretch_check", "sgpu_stretch_coeffs", "sgpu_autostretch_params", "sgpu_stretch_planes_device",
     "sgpu_stretch_last_kernel_ms",
+    "sgpu_epf_check", "sgpu_epf_planes_device", "sgpu_epf_last_kernel_ms",
     "sgpu_star_default_params", "sgpu_match_default_params", "sgpu_star_smooth_table", "sgpu_find_stars_device",
     "sgpu_star_last_candidates", "sgpu_star_last_kernel_ms", "sgpu_match_stars",
     "sgpu_psf_default_params", "sgpu_fit_stars_device", "sgpu_psf_last_kernel_ms",
@@ -446,6 +447,13 @@ def lib():
                                                  C.c_long]
         L.sgpu_stretch_last_kernel_ms.restype = i
         L.sgpu_stretch_last_kernel_ms.argtypes = [vp, C.POINTER(f), pi]
+        L.sgpu_epf_check.restype = i
+        L.sgpu_epf_check.argtypes = [i, i, i, i, C.c_double, C.c_double, f]
+        L.sgpu_epf_planes_device.restype = i
+        L.sgpu_epf_planes_device.argtypes = [vp, vp, i, i, i, i, C.c_long, vp, i, C.c_long, i, i, C.c_double,
+                                             C.c_double, f, vp, C.c_long]
+        L.sgpu_epf_last_kernel_ms.restype = i
+        L.sgpu_epf_last_kernel_ms.argtypes = [vp, C.POINTER(f), pi, pi]
         L.sgpu_star_default_params.restype = None
         L.sgpu_star_default_params.argtypes = [C.POINTER(StarParams)]
         L.sgpu_match_default_params.restype = None

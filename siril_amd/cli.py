@@ -41,6 +41,12 @@ sharpens with them: the planes of an n-layer transform weighted by c1 .. cn and 
 with the sample by modulation in [0, 1], N = 1 .. 8 passes; writes one 32-bit image, <stem>_fmedian.fit unless -out=
 names it.
 
+`python -m siril_amd.cli epf <image> [-guided] [-d=N] [-si=X] [-ss=X] [-mod=X] [-guideimage=FILE] [-out=FILE]`: the
+edge-preserving filter (siril_amd/filters.py) of every layer of an image: with -guided a guided filter
+(eps = si^2, si in [0, 1] sample units, a d x d window, d odd in 3 .. 25 or 0 for 2 round(1.5 ss) + 1) steered by the
+image itself or by -guideimage=; writes one 32-bit image, <stem>_epf.fit unless -out= names it.  Without -guided the
+command means the bilateral filter, which is not built and is refused.
+
 The stretches (siril_amd/stretch.py), each on every layer of an image, each writing one 32-bit image,
 <stem>_<command>.fit unless -out= names it:
 `python -m siril_amd.cli mtf <image> <low> <mid> <high> [channels] [-out=FILE]`,
@@ -93,6 +99,12 @@ def main(argv=None):
         t0 = time.perf_counter()
         out = run_fmedian(argv)
         print(f"Median filtered to {out} in {time.perf_counter() - t0:.3f} s")
+        return 0
+    if argv and argv[0] == "epf":
+        from siril_amd.filters import run_epf
+        t0 = time.perf_counter()
+        out = run_epf(argv)
+        print(f"Edge-preserving filtered to {out} in {time.perf_counter() - t0:.3f} s")
         return 0
     if argv and argv[0] in ("mtf", "autostretch", "linstretch", "asinh", "ght", "invght", "modasinh", "invmodasinh"):
         from siril_amd.stretch import run_stretch

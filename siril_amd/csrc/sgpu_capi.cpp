@@ -243,6 +243,8 @@ void sgpu_release(sgpu_context *c) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->str_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->epf_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->own) (void)hipStreamDestroy(c->own);
     delete c;
 }

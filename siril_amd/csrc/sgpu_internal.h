@@ -176,6 +176,11 @@ struct sgpu_context {
     // stretches: one event before the first launch of a call, one after the last
     hipEvent_t str_ev[2] = {};
     int str_launches = 0;
+    // edge-preserving filters: the guided filter's a and b, two float planes per input plane
+    sgpu_host::DevBuf epf_ws;
+    hipEvent_t epf_ev[SGPU_EPF_MAX_LAUNCHES + 1] = {};     // one before every launch of a call, one after the last
+    int epf_what[SGPU_EPF_MAX_LAUNCHES] = {};              // 100*kernel + d, per launch
+    int epf_launches = 0;
 
     void release_all() {
         for (sgpu_host::DevBuf *b : {&fb_list, &fb_count, &counts, &scratch, &scale, &offset, &mul,
@@ -184,7 +189,7 @@ struct sgpu_context {
                                      &dft_frames, &rl_u, &rl_e, &rl_f, &rl_r, &rl_w, &rl_taps, &rl_small,
                                      &rl_io, &rl_reg, &rl_gxy, &rlf_t1, &rlf_t2, &rlf_ka, &rlf_kb, &rlf_kt, &rlf_tw1, &rlf_tw2, &dm_ws, &dm_mm, &dm_io, &ns_state, &ns_hist, &ns_part, &ns_io, &bn_rows, &qe_buf, &qe_part, &qe_io, &onorm, &ov_ws, &ov_tab,
                                      &fb2_list, &fb2_count, &wz_ws, &wz_cnt, &fe_tab, &fe_dt, &cfa_tmp, &cstripe, &warp_ws, &drz_ws, &cal_rows, &cal_k, &cal_cnt, &cal_plan,
-                                     &star_tc, &star_slots, &star_fp, &star_out, &psf_jobs, &psf_out, &bkg_ws, &bkg_mom, &rbf_ws, &rbf_res, &wav_ws, &med_ws,
+                                     &star_tc, &star_slots, &star_fp, &star_out, &psf_jobs, &psf_out, &bkg_ws, &bkg_mom, &rbf_ws, &rbf_res, &wav_ws, &med_ws, &epf_ws,
                                      &seq_in[0], &seq_in[1], &seq_out, &seq_lo, &seq_hi, &seq_cnt})
             b->release();
         seq_pin[0].release();
